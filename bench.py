@@ -12,6 +12,11 @@ barrier and the max-over-ranks time.
     python bench.py [--gpus N] [--steps K] [--warmup W] [--settle-ms 200] [--n 4096] [--q 2013265921]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
+A plain run does what the headline figure needs and no more: set up, settle, W warm-up steps, the
+K timed steps, the result line.  --dump-outputs DIR also writes what the last timed step computed.
+--full adds the legs that take runs of their own after the timed region: board power, the in-kernel
+clock of the diagnostic build and the CPU baseline (each with its own switch, as before).
+
 Prints ONE JSON line on rank 0 (fields documented in DESIGN.md §Measurement).
 """
 import argparse
@@ -136,11 +141,21 @@ def parse(argv=None):
                     help="multiply (the BASELINE metric); forward / inverse / pointwise time the "
                          "standalone batched entry points (nttmul_forward/inverse/pointwise_batch_"
                          "device, SURVEY 8(f) row 1) with the same contract, not the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs that are not part of the "
+                         "headline figure: the board-power probe (--power-seconds), the in-kernel "
+                         "clock of the diagnostic build (--clock-seconds) and the CPU baseline "
+                         "(--cpu-seconds, --no-cpu-baseline); without it none of them runs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed to "
+                         "DIR/<name>.npy (float64; a fixed, seeded sample of the rows when the "
+                         "output is larger than the dump budget)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--host-io", action="store_true",
                     help="also time the host-buffer ABI path (PCIe-inclusive; never the value)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="target wall time of the CPU-baseline sample")
+                    help="with --full: target wall time of the CPU-baseline sample")
     ap.add_argument("--rotate", type=int, default=0,
                     help="cycle the steps over this many distinct (a, b, c) buffer sets, so a "
                          "batch smaller than the Infinity Cache is still read from HBM "
@@ -153,12 +168,12 @@ def parse(argv=None):
                     help="before the W warm-up steps, run the hot path untimed for this long so "
                          "the card leaves its idle clock state (reported as 'settle'; 0 disables)")
     ap.add_argument("--power-seconds", type=float, default=4.0,
-                    help="after the timed region, keep stepping this long while amd-smi samples "
-                         "board power and clocks (rank 0 at N=1; 0 disables)")
+                    help="with --full: after the timed region, keep stepping this long while "
+                         "amd-smi samples board power and clocks (rank 0 at N=1; 0 disables)")
     ap.add_argument("--clock-seconds", type=float, default=2.0,
-                    help="after the power probe, run the same product from the diagnostic build "
-                         "lib/libnttmul_diag.so this long and report the in-kernel clock "
-                         "(rank 0 at N=1; 0 disables)")
+                    help="with --full: after the power probe, run the same product from the "
+                         "diagnostic build lib/libnttmul_diag.so this long and report the "
+                         "in-kernel clock (rank 0 at N=1; 0 disables)")
     ap.add_argument("--dump-samples", default="",
                     help="write <prefix>.rank<r>.npz with sampled products of this rank's slice "
                          "(checked against the oracle by tests/test_gpu_parity.py)")
@@ -430,6 +445,44 @@ def buffer_sets(step_bytes: int, requested: int = 0) -> int:
     return -(-3 * IC_BYTES // step_bytes) if step_bytes <= IC_BYTES else 1
 
 
+DUMP_BYTES = 32 << 20       # --dump-outputs: bytes of coefficient arrays written per rank
+
+
+def dump_rows(count: int, n: int, wb: int):
+    """Rows (polynomials of this rank's slice) that --dump-outputs writes: all of them when they
+    fit DUMP_BYTES as float64 (64-bit words take two arrays), else the first, the last and a
+    sample drawn without replacement from a fixed seed; sorted, the same for every run and build."""
+    import numpy as np
+    k = max(2, DUMP_BYTES // (n * 8 * (1 if wb == 32 else 2)))
+    if count <= k:
+        return np.arange(count, dtype=np.int64)
+    pick = np.random.RandomState(SEED & 0xFFFFFFFF).choice(count, size=k - 2, replace=False)
+    return np.unique(np.concatenate(([0, count - 1], pick))).astype(np.int64)
+
+
+def dump_outputs(dirname: str, c, count: int, n: int, wb: int, rank: int, world: int):
+    """Write the result buffer of the last timed step -- what the caller of the timed entry point
+    receives -- as float64 arrays of shape (rows, n) under `dirname`: c.npy for 32-bit words
+    (exact), c_lo.npy and c_hi.npy (low and high 32 bits, each exact) for 64-bit words, and
+    rows.npy with the rows' indices in this rank's slice.  Ranks of an N > 1 run write
+    <name>.rank<r>.npy.  Returns the names written."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    rows = dump_rows(count, n, wb)
+    host = c.view(count, n)[torch.from_numpy(rows).to(c.device)].cpu().numpy()
+    if wb == 32:
+        arrays = {"c": host.view(np.uint32)}
+    else:
+        u = host.view(np.uint64)
+        arrays = {"c_lo": u & np.uint64(0xFFFFFFFF), "c_hi": u >> np.uint64(32)}
+    arrays["rows"] = rows
+    tag = f".rank{rank}" if world > 1 else ""
+    for name, x in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), x.astype(np.float64))
+    return sorted(f"{name}{tag}.npy" for name in arrays)
+
+
 def _num(x):
     return x if isinstance(x, (int, float)) and not isinstance(x, bool) else None
 
@@ -697,6 +750,11 @@ def main(argv=None):
         np.savez(f"{args.dump_samples}.rank{rank}.npz", p0=p0, p1=p1, idx=np.array(idx),
                  c=rows, n=n, q=q, world=world, global_batch=global_batch)
 
+    dumped = None
+    if args.dump_outputs:  # the result buffer the last timed step wrote
+        dumped = dump_outputs(args.dump_outputs, sets[(state["i"] - 1) % rotate][2], count, n, wb,
+                              rank, world)
+
     if world > 1:
         # every rank's GPU work is done: rank 0 alone goes on to the CPU baseline (the others
         # leave), so its sample runs on a quiet host at every N
@@ -725,6 +783,7 @@ def main(argv=None):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "settle": {"steps": settle_steps, "ms": round(settle_ms, 1),
                        "note": "untimed hot-path steps before the W warm-up steps, so the card "
                                "is past its idle clock ramp (DESIGN.md §5 'Settle phase')"},
@@ -776,7 +835,11 @@ def main(argv=None):
         vb = load_valu_bound(n, q, kernels) if kernels else None
         if vb:  # the bound that binds: integer VALU issue, from this build's ISA
             line["valu_roofline"] = valu_roofline(vb, count, kern_ms, kernels)
-        if world == 1 and args.power_seconds > 0:
+        if dumped:
+            line["outputs"] = {"dir": args.dump_outputs, "files": dumped,
+                               "note": "float64 rows of the last timed step's result buffer "
+                                       "(bench.dump_outputs)"}
+        if args.full and world == 1 and args.power_seconds > 0:
             try:
                 props = torch.cuda.get_device_properties(dev)
                 bdf = (f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:"
@@ -789,7 +852,7 @@ def main(argv=None):
                                             units_per_step=count)
             except Exception as e:  # reported evidence, never required
                 line["power"] = {"error": str(e)}
-        if world == 1 and args.clock_seconds > 0 and product:
+        if args.full and world == 1 and args.clock_seconds > 0 and product:
             a, b, c = sets[0]
             try:
                 clk = diag_clock(n, q, wb, count, a, b, c, devno, sptr,
@@ -811,7 +874,7 @@ def main(argv=None):
         if args.host_io and product:
             a, b, _ = sets[0]
             line["host_io"] = host_io(ctx, a, b, count, n, wb)
-        if not args.no_cpu_baseline and product:
+        if args.full and not args.no_cpu_baseline and product:
             try:  # rank 0 only, after every rank's GPU work (the final barrier above)
                 line["cpu_baseline"] = cpu_baseline(n, q, args.cpu_seconds)
                 if line["cpu_baseline"] and world > 1:

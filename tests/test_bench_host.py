@@ -5,6 +5,7 @@ import json
 import os
 import struct
 
+import numpy as np
 import pytest
 
 import bench
@@ -217,6 +218,32 @@ def test_op_defaults_to_the_product():
     assert bench.parse(["--op", "inverse"]).op == "inverse"
     with pytest.raises(SystemExit):
         bench.parse(["--op", "square"])
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """Without --full the legs after the timed region (power, in-kernel clock, CPU baseline) stay
+    off; their own switches keep their defaults for a --full run."""
+    plain = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and plain.dump_outputs == "" and plain.steps == 20
+    full = bench.parse(["--full"])
+    assert full.full is True and not full.no_cpu_baseline
+    assert full.power_seconds > 0 and full.clock_seconds > 0 and full.cpu_seconds > 0
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_rows_are_a_fixed_sample_within_the_budget():
+    """--dump-outputs: every row when the output fits the budget, else a sorted sample with both
+    ends that is the same on every call; the arrays stay under 64 MB at C3, C2 and C5."""
+    assert np.array_equal(bench.dump_rows(5, 4096, 32), np.arange(5))
+    assert np.array_equal(bench.dump_rows(4096, 1024, 32), np.arange(4096))     # C2: 32 MiB, all
+    for count, n, wb in ((65536, 4096, 32), (131072, 4096, 32), (1024, 65536, 64), (3000, 4096, 64)):
+        rows = bench.dump_rows(count, n, wb)
+        assert np.array_equal(rows, bench.dump_rows(count, n, wb))
+        assert rows[0] == 0 and rows[-1] == count - 1 and np.all(np.diff(rows) > 0)
+        assert len(rows) < count
+        per_row = n * 8 * (1 if wb == 32 else 2)
+        assert bench.DUMP_BYTES // 2 < len(rows) * per_row <= bench.DUMP_BYTES
+        assert (len(rows) * (per_row + 8)) < 64e6
 
 
 # what the library dispatches for the three bench configurations (pinned on the GPU by

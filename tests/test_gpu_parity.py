@@ -929,6 +929,48 @@ def test_bench_host_io_leg(torch_cuda):
     assert np.array_equal(got, c.cpu().numpy().view(np.uint32).reshape(batch, n))
 
 
+@pytest.mark.parametrize("n,q,batch", [(4096, Q31, 1100), (1024, Q62, 2100)])
+def test_bench_plain_run_dumps_its_outputs(n, q, batch, tmp_path, capsys, torch_cuda):
+    """A plain bench run (no --full) times exactly --steps steps, runs none of the legs behind
+    --full, and with --dump-outputs writes float64 rows of the last timed step's result buffer
+    (32-bit words as c.npy; 64-bit words as their exact halves c_lo.npy / c_hi.npy), here a
+    seeded sample of the batch; every dumped row is the oracle's product at its counter position,
+    and a second run with the same arguments writes the same arrays."""
+    import bench
+    wb = 32 if q < (1 << 32) else 64
+    P = O.Plan(n, q)
+    seen = []
+    for run in ("one", "two"):
+        d = tmp_path / run
+        bench.main(["--gpus", "1", "--steps", "3", "--warmup", "2", "--settle-ms", "0", "--n", str(n),
+                    "--q", str(q), "--batch-per-gpu", str(batch), "--rotate", "2",
+                    "--dump-outputs", str(d)])
+        line = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["full"] is False
+        assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(batch / line["ms_per_step"] * 1e3)
+        assert line["cpu_baseline"] is None
+        assert not {"power", "in_kernel_clock", "host_io"} & set(line)
+        names = ["c.npy", "rows.npy"] if wb == 32 else ["c_hi.npy", "c_lo.npy", "rows.npy"]
+        assert sorted(os.listdir(d)) == names == line["outputs"]["files"]
+        arrs = {k: np.load(d / k) for k in names}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) < 64e6
+        seen.append(arrs)
+    rows = seen[0]["rows.npy"].astype(np.int64)
+    assert np.array_equal(rows, bench.dump_rows(batch, n, wb)) and 2 < len(rows) < batch
+    if wb == 32:
+        got = seen[0]["c.npy"].astype(np.uint64)
+    else:
+        got = (seen[0]["c_hi.npy"].astype(np.uint64) << np.uint64(32)) | seen[0]["c_lo.npy"].astype(np.uint64)
+    assert got.shape == (len(rows), n)
+    step = max(1, len(rows) // 16)
+    for i in list(range(0, len(rows), step)) + [len(rows) - 1]:
+        ea, eb = O.fill_inputs(n, q, int(rows[i]), 1, seed=bench.SEED)
+        assert np.array_equal(got[i], P.product_merged(ea[0], eb[0])), int(rows[i])
+    for k in seen[0]:
+        assert np.array_equal(seen[0][k], seen[1][k]), k
+
+
 # ---------------------------------------------------------------------------------------------
 # The reference's whole transform wrapper set (NTT/ntt256.h:20-69) and its general form
 # ---------------------------------------------------------------------------------------------
@@ -1018,7 +1060,7 @@ def test_bench_ranks_on_one_gpu(world, batch, tmp_path, torch_cuda):
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
          str(world), "--master-addr", "127.0.0.1", "--master-port", str(port),
          os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-         "--settle-ms", "20", "--cpu-seconds", "0.5", "--dump-samples", prefix]
+         "--settle-ms", "20", "--full", "--cpu-seconds", "0.5", "--dump-samples", prefix]
         + (["--batch-per-gpu", str(batch)] if batch else []),
         capture_output=True, text=True, timeout=300, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]

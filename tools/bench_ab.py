@@ -29,7 +29,7 @@ def main():
     import io
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(sys.argv[2:] + ["--clock-seconds", "0", "--no-cpu-baseline"])
+        bench.main(sys.argv[2:] + ["--full", "--clock-seconds", "0", "--no-cpu-baseline"])
     line = json.loads([ln for ln in buf.getvalue().splitlines() if ln.startswith("{")][-1])
     for k in ("build", "valu_roofline", "in_kernel_clock"):
         line.pop(k, None)

@@ -15,6 +15,7 @@ Inputs (all committed or rebuildable):
                                             socket power, gfx clock, UMC activity per run
   --listing-fit   `hipcc -S` of the round-5 kernels the variants ran (commit 97692dc)
   --listing       the listing of the kernels the bench line ran (`make asm` of this tree)
+  --bench         a C5 line of `bench.py --full` (its `power` and `in_kernel_clock` are read)
 HBM bytes per product of a variant: the bytes it still sends to memory (base: the PMC-measured
 4.72 MB, 2.5 MiB read and 2 MiB written); the redirected intermediates are charged at the L2
 stream energy.  Energies are per product, in uJ."""

@@ -16,7 +16,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 tail -1 $OUT/smoke.txt
 line() {  # name, timeout, bench args...
   local name=$1 t=$2; shift 2
-  timeout -k 10 $t python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { tail -20 $OUT/$name.err; exit 1; }
+  timeout -k 10 $t python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { tail -20 $OUT/$name.err; exit 1; }
   python3 -c "import json; d=json.loads(open('$OUT/$name.json').read().splitlines()[-1]); r=d['roofline']; print('$name', round(d['value']/1e6,4), 'M/s', round(r['frac'],4), round(r['kernel_ms'],5), 'traffic', r['traffic'] is not None, 'valu', 'valu_roofline' in d)"
 }
 line c3_driver_cmd 300 --gpus 1 --steps 20 --warmup 5

@@ -19,7 +19,7 @@ one() {  # cfg name, bench args...
   local OUT=gpurun_out/$TAG/$cfg
   mkdir -p $OUT
   echo "== $cfg" >&2
-  run 300 python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+  run 300 python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
   tail -c 700 $OUT/bench.json >&2
   run 300 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o trace --output-format csv -- \
     python3 bench.py --no-cpu-baseline --power-seconds 0 --clock-seconds 0 "$@" > $OUT/trace.log 2>&1
