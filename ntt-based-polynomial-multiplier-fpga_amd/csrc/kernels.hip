@@ -134,10 +134,8 @@ static hipError_t launch_polymul_(const LaunchTables &T, const void *a, const vo
                                   size_t batch, int io_bits, void **scr, hipStream_t s) {
   if (T.word_bits == 32) {  // 64-bit storage of a q < 2^32 product: same 32-bit arithmetic
     switch (a32_kind(T.q)) {
-      case A32Kind::Harvey: return polymul_io<Arith32H>(T, a, b, c, batch, io_bits, scr, s);
       case A32Kind::Wide: return polymul_io<Arith32W>(T, a, b, c, batch, io_bits, scr, s);
       case A32Kind::Plantard: return polymul_io<Arith32P>(T, a, b, c, batch, io_bits, scr, s);
-      case A32Kind::Mont: return polymul_io<Arith32>(T, a, b, c, batch, io_bits, scr, s);
     }
   }
   return polymul_io<Arith64>(T, a, b, c, batch, io_bits, scr, s);
@@ -280,10 +278,8 @@ static hipError_t launch_xform_dir(const LaunchTables &T, const void *in, void *
                                    int io_bits, void **scr, hipStream_t s) {
   if (T.word_bits == 32) {
     switch (a32_kind(T.q)) {
-      case A32Kind::Harvey: return xform_io<Arith32H, DIR>(T, in, out, batch, io_bits, scr, s);
       case A32Kind::Wide: return xform_io<Arith32W, DIR>(T, in, out, batch, io_bits, scr, s);
       case A32Kind::Plantard: return xform_io<Arith32P, DIR>(T, in, out, batch, io_bits, scr, s);
-      case A32Kind::Mont: return xform_io<Arith32, DIR>(T, in, out, batch, io_bits, scr, s);
     }
   }
   return xform_io<Arith64, DIR>(T, in, out, batch, io_bits, scr, s);

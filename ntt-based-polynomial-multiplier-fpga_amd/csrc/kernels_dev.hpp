@@ -30,56 +30,6 @@
 #include "launch.hpp"
 #include "modarith.hpp"
 
-// LDS regions per polynomial pair for 32-bit words (2: a and b exchanged together; 1: in turn,
-// half the LDS).  One region: 17 KiB per n = 4096 block, 7 blocks (VGPR-limited) instead of 4 per
-// CU; with the Plantard kernel -2 % at C3, -1 % at n = 1024 x 262144 and n = 65536, C2 unchanged
-// (profiles/r2/plantard/ab1.txt).  64-bit words always use one region (C5 -6 %, tools/c5_ab.sh)
-#ifndef NTTMUL_LDS_REGIONS
-#define NTTMUL_LDS_REGIONS 1
-#endif
-// a, b, c streams of the one-product-per-block u32 products (n = 4096, 1024) as buffer loads /
-// stores on a block-uniform descriptor with cache-policy bits aux = NTTMUL_CPOL (1 sc0, 2 nt,
-// 16 sc1; -1: global loads as below).  C3 kbench A/B (profiles/r2/cpol_ab.txt, identical
-// checksums): nt -1.2 % against the global nt loads (the 32-bit voffset form drops the 64-bit
-// address adds: 1,940 VALU per wave instead of 1,951); nt with sc0 / sc1 the same as nt alone;
-// plain (0) +0.3 %, sc1 alone +0.1 %
-#ifndef NTTMUL_CPOL
-#define NTTMUL_CPOL 2
-#endif
-#ifndef NTTMUL_CPOL_ST
-#define NTTMUL_CPOL_ST NTTMUL_CPOL
-#endif
-// non-temporal loads/stores of the coefficient streams in k_rows
-#ifndef NTTMUL_NT
-#define NTTMUL_NT 1
-#endif
-// n = 1024: a's loads first and a's forward transform before b's (k_rows kSplitAB)
-#ifndef NTTMUL_SPLIT_AB
-#define NTTMUL_SPLIT_AB 0
-#endif
-// NTTMUL_A32H / NTTMUL_A32_PLANTARD (which 32-bit class takes which q): arith_select.hpp
-// incomplete transforms in the product kernel: the last D = A::kBaseD stages become base
-// multiplications of 2^D-coefficient blocks (0: full transforms + pointwise Montgomery product)
-#ifndef NTTMUL_BASE_D
-#define NTTMUL_BASE_D 1
-#endif
-// skip the reduction of X in the first forward stage (input canonical by contract)
-#ifndef NTTMUL_FIRST_XC
-#define NTTMUL_FIRST_XC 1
-#endif
-// __launch_bounds__ minimum waves per SIMD for k_rows (1 = no constraint)
-#ifndef NTTMUL_MIN_WAVES
-#define NTTMUL_MIN_WAVES 1
-#endif
-// conflict-free LDS padding for the group 0 <-> 1 exchanges (Groups::padx; 0 = e + (e >> 4))
-#ifndef NTTMUL_PAD0
-#define NTTMUL_PAD0 1
-#endif
-// two-term pads at n = 512 / 1024 (Groups::PS2)
-#ifndef NTTMUL_PAD2
-#define NTTMUL_PAD2 1
-#endif
-// NTTMUL_SPLIT16 (column stages of the n = 65536 multi-pass product): arith_select.hpp
 // Instrumentation points, the identity here.  tools/kbench/kb_hooks.hpp defines them before it
 // includes this header, to build wrong-result pricing variants of these same kernels (loads or
 // stores redirected into an L2- or Infinity-Cache-sized window, inputs synthesised instead of
@@ -137,9 +87,6 @@
 
 namespace nttmul {
 
-template <class W>
-__host__ __device__ constexpr int lds_regions() { return sizeof(W) == 8 ? 1 : NTTMUL_LDS_REGIONS; }
-
 template <class A>
 struct KParams {
   A ar;
@@ -163,20 +110,8 @@ static void describe_add(const std::string &k) {
 // ---------------------------------------------------------------------------------------------
 // Layout algebra of the register groups (all compile-time except the per-thread base)
 // ---------------------------------------------------------------------------------------------
-// WT (wave-typed layouts, n = 4096 rows of the Plantard kernels, NTTMUL_WAVE_TYPED): groups 1
-// and 2 take their element bits from the thread index in another order, so that the bit that
-// says whether the previous group's last forward stage wrote an element as a sum or as a
-// difference (element bit 8 after group 0, bit 4 after group 1) is thread bit 6 -- the same for
-// a whole wave.  Those last stages can then leave their differences signed across the LDS
-// exchange (one instruction less per butterfly, -0.85 % time by ablation, profiles/r3/c3/) and
-// the next group's first stage picks its operand type with one wave-uniform branch.  Group 1:
-// thread bits 0-3 -> element bits 0-3, 4 -> 9, 5 -> 10, 6 -> 8, 7 -> 11; group 2: thread bits
-// 0-5 -> element bits 5-10, 6 -> 4, 7 -> 11.  Both exchanges then pad e + (e >> 5), which the bank
-// census (tests/test_layout.py) finds conflict-free for both layouts of each exchange.
-// (NTTMUL_WAVE_TYPED: arith_select.hpp, shared with the planner's twiddle forms)
-template <int LOGS, bool WT = false>
+template <int LOGS>
 struct Groups {
-  static_assert(!WT || LOGS == 12, "wave-typed layouts are defined for 4096-coefficient rows");
   static constexpr int N = 1 << LOGS;
   static constexpr int G = (LOGS + 3) / 4;
   static constexpr int S(int g) { return LOGS / G + (g < LOGS % G ? 1 : 0); }
@@ -196,18 +131,7 @@ struct Groups {
     if (lr >= LNS(g)) return sidx + (m << lr);
     return ((sidx >> lr) << (lr + s)) + (sidx & ((1 << lr) - 1)) + (m << lr);
   }
-  __host__ __device__ static constexpr int base_wt(int g, int j) {
-    return g == 1 ? (j & 15) + (((j >> 4) & 1) << 9) + (((j >> 5) & 1) << 10) +
-                        (((j >> 6) & 1) << 8) + (((j >> 7) & 1) << 11)
-                  : ((j & 63) << 5) + (((j >> 6) & 1) << 4) + (((j >> 7) & 1) << 11);
-  }
-  // WT: the operand type (0 sum, 1 difference) of the elements a thread holds at the start of
-  // register group g >= 1; thread bit 6, uniform over the wave
-  __device__ static __forceinline__ int wave_type(int j) {
-    return __builtin_amdgcn_readfirstlane((j >> 6) & 1);
-  }
   __device__ static __forceinline__ int base(int g, int j) {
-    if (WT && g > 0) return base_wt(g, j);
     int lr = LR(g), s = S(g), lns = LNS(g);
     if (lr >= lns) {
       int set0 = j << lns;
@@ -220,7 +144,6 @@ struct Groups {
     int lr = LR(g), lns = LNS(g);
     int sidx = k % NS(g);
     if (g == 0) return 0;
-    if (WT) return base_wt(g, j) >> (lr + S(g));  // the element bits above the group's stages
     if (lr >= lns) return (j << lns) >> lr;
     return (j << (lns - lr)) + (sidx >> lr);
   }
@@ -240,17 +163,15 @@ struct Groups {
   // n = 1024 and 512 (one wave per product, three groups of 3-4 stages) take a second term,
   // e + ((e >> s) << t) + ((e >> s2) << t2), found by the same census (tests/test_layout.py): the
   // single-term pads left 32 extra cycles on each exchange at n = 1024 (PMC: 33 % of LDS cycles)
-  static constexpr bool kPad0 = NTTMUL_PAD0 && LOGS >= 10 && G > 2;
-  static constexpr bool kPad2 = NTTMUL_PAD0 && NTTMUL_PAD2 && (LOGS == 10 || LOGS == 9);
+  static constexpr bool kPad0 = LOGS >= 10 && G > 2;
+  static constexpr bool kPad2 = LOGS == 10 || LOGS == 9;
   static constexpr int PS(int x) {
-    return WT ? 5
-              : kPad2 ? (LOGS == 10 ? (x == 0 ? 6 : 4) : (x == 0 ? 5 : 4))
-                      : (x == 0 && kPad0 ? LOGS - 4 : 4);
+    return kPad2 ? (LOGS == 10 ? (x == 0 ? 6 : 4) : (x == 0 ? 5 : 4))
+                 : (x == 0 && kPad0 ? LOGS - 4 : 4);
   }
   static constexpr int PT(int x) {
-    return WT ? 0
-              : kPad2 ? (LOGS == 10 ? (x == 0 ? 3 : 1) : (x == 0 ? 0 : 1))
-                      : (x == 0 && kPad0 ? LOGS - 8 : 0);
+    return kPad2 ? (LOGS == 10 ? (x == 0 ? 3 : 1) : (x == 0 ? 0 : 1))
+                 : (x == 0 && kPad0 ? LOGS - 8 : 0);
   }
   static constexpr int PS2(int x) { return kPad2 ? (LOGS == 10 ? 8 : (x == 0 ? 7 : 8)) : 31; }
   template <int X>
@@ -276,44 +197,21 @@ static_assert(groups_agree<8>() && groups_agree<9>() && groups_agree<10>() && gr
 template <class W, class T>
 __device__ __forceinline__ W to_word(T v) { return (W)v; }
 
-// Arith32P's typed CT (modarith.hpp Arith32P::ct<XC, XN, YN>)
+// the Plantard classes: typed CT (modarith.hpp Arith32P::ct<XC, XN, YN>), signed-form twiddles
 template <class A>
 struct IsPlantard : std::false_type {};
 template <>
 struct IsPlantard<Arith32P> : std::true_type {};
 template <>
 struct IsPlantard<Arith32P3> : std::true_type {};
-template <> struct AName<Arith32> { static constexpr const char *v = "Arith32"; };
-template <> struct AName<Arith32H> { static constexpr const char *v = "Arith32H"; };
 template <> struct AName<Arith32P> { static constexpr const char *v = "Arith32P"; };
 template <> struct AName<Arith32P3> { static constexpr const char *v = "Arith32P3"; };
 template <> struct AName<Arith32W> { static constexpr const char *v = "Arith32W"; };
 template <> struct AName<Arith64> { static constexpr const char *v = "Arith64"; };
-template <class A>
-__host__ __device__ constexpr bool kTypedP() {
-  if constexpr (IsPlantard<A>::value) return A::kTypedP;
-  return false;
-}
-// wave-typed layouts (Groups WT) for the typed Plantard kernels' 4096-coefficient rows; the
-// planner stores the matching twiddle forms (arith_select.hpp p_signed_fw_entry)
-template <class A, int LOGS>
-__host__ __device__ constexpr bool kWT() {
-  return wave_typed_rows(LOGS) && kTypedP<A>() && NTTMUL_P_TYPED >= 2;
-}
 
-// Coefficient streams are touched once per product: NTTMUL_NT marks them non-temporal.  The row
-// pass of a multi-pass product (L1 > 0) reads and writes intermediates that the column passes
-// touch again, so NTTMUL_NT_MP (default 0) keeps those accesses temporal: a sub-batch whose
-// scratch fits the Infinity Cache can then stay there between the three launches.
-#ifndef NTTMUL_NT_MP
-#define NTTMUL_NT_MP 0
-#endif
-// column passes of the multi-pass product through non-temporal loads / stores: C5 1.375-1.383
-// vs 1.417-1.434 ms (kbench A/B, identical checksums, profiles/r2/nt_cols/); the row pass
-// keeps its intermediates temporal (NTTMUL_NT_MP = 1 measured 1.400 ms)
-#ifndef NTTMUL_NT_COLS
-#define NTTMUL_NT_COLS 1
-#endif
+// Non-temporal (NT) or plain access to a coefficient stream.  The fused products' streams and the
+// multi-pass product's column passes are non-temporal; its row pass keeps the intermediates
+// temporal (k_rows kNT)
 template <bool NT, class T>
 __device__ __forceinline__ T ld_stream(const T *p) {
   if constexpr (NT) return __builtin_nontemporal_load(p);
@@ -327,15 +225,16 @@ __device__ __forceinline__ void st_stream(T *p, T v) {
     *p = v;
 }
 
-// Buffer-resource streams (NTTMUL_CPOL): a descriptor over one block-uniform span of words and
-// 32-bit per-lane byte offsets; AUX = the cache-policy bits of the load / store
+// Buffer-resource streams: a descriptor over one block-uniform span of words and 32-bit per-lane
+// byte offsets; AUX = the cache-policy bits of the load / store (1 sc0, 2 nt, 16 sc1)
+constexpr int kAuxNt = 2;
 template <class T>
 __device__ __forceinline__ auto span_rsrc(const T *p, size_t words) {
   return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)(words * sizeof(T)), 0x00020000);
 }
-// SOFF: a wave-uniform byte offset passed as the instruction's scalar offset (NTTMUL_BUF_SOFF:
-// the register's constant part, so the per-lane offset is the thread's base alone and no VALU
-// add / or forms each register's address)
+// soff: a wave-uniform byte offset passed as the instruction's scalar offset (the register's
+// constant part, so the per-lane offset is the thread's base alone and no VALU add / or forms
+// each register's address)
 template <int AUX, class R>
 __device__ __forceinline__ uint32_t buf_ld32(R r, int byte_off, int soff = 0) {
   return __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, soff, AUX);
@@ -344,9 +243,9 @@ template <int AUX, class R>
 __device__ __forceinline__ void buf_st32(R r, int byte_off, uint32_t v, int soff = 0) {
   __builtin_amdgcn_raw_buffer_store_b32(v, r, byte_off, soff, AUX);
 }
-#ifndef NTTMUL_BUF_SOFF
-#define NTTMUL_BUF_SOFF 1
-#endif
+// The square split's passes (k_cols8 and its row pass, 64-bit words) use these on a descriptor
+// per polynomial (block-uniform) with 32-bit lane offsets and each register's constant offset in
+// the scalar offset, instead of a 64-bit address per register
 template <int AUX, class R>
 __device__ __forceinline__ uint64_t buf_ld64(R r, int byte_off, int soff) {
   typedef unsigned int u2 __attribute__((ext_vector_type(2)));
@@ -359,26 +258,16 @@ __device__ __forceinline__ void buf_st64(R r, int byte_off, uint64_t v, int soff
   const u2 w = {(unsigned)v, (unsigned)(v >> 32)};
   __builtin_amdgcn_raw_buffer_store_b64(w, r, byte_off, soff, AUX);
 }
-// The square split's column passes (k_cols8, 64-bit words) through buffer instructions on a
-// descriptor per polynomial (block-uniform) with 32-bit lane offsets and each register's constant
-// offset in the scalar offset, instead of a 64-bit address per register (NTTMUL_C5_BUF; with the
-// row pass in the same form: C5 1.221 vs 1.243 ms, kbench A/B interleaved, identical checksums,
-// profiles/r6/ab_c5_buf.json)
-#ifndef NTTMUL_C5_BUF
-#define NTTMUL_C5_BUF 1
-#endif
 
 // One forward CT stage l of group g on NPOLY (1 or 2) polynomials (same twiddles); the twiddles
-// of the group's last performed stage are kept in zw[X register] (see base_mult).  TIN: under the
-// wave-typed layouts (kWT) the operand type of the first stage of groups g >= 1, chosen by the
-// caller's wave-uniform branch (1: the previous group's differences, left signed).
-template <class A, int LOGS, int g, int NPOLY, int SKIP, int TIN>
+// of the group's last performed stage are kept in zw[X register] (see base_mult).
+template <class A, int LOGS, int g, int NPOLY, int SKIP>
 __device__ __forceinline__ void fwd_stage(const A &ar, typename A::word (&x)[16],
                                           typename A::word (&y)[16],
                                           const TwPair<typename A::word> *__restrict__ tw, int j,
                                           int row, int l1, TwPair<typename A::word> (&zw)[16],
                                           int l) {
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int S = Gr::S(g), st0 = Gr::ST0(g), ns = Gr::NS(g);
   const int dist = 8 >> l;
   const int st = st0 + l;
@@ -388,51 +277,22 @@ __device__ __forceinline__ void fwd_stage(const A &ar, typename A::word (&x)[16]
     if (k & dist) continue;
     const int m = k / ns;
     const int idx = tbase + (Gr::blk(g, j, k) << l) + (m >> (S - l));
-    if constexpr (A::kTyped) {
-      // operand type: bit 2 dist of k says the previous stage of this group wrote it as Y
-      // (N-type); the group's first stage reads P-type; its last writes P-type
-      const bool in_n = l > 0 && (k & (2 * dist));
-      const bool out_p = l == S - SKIP - 1;
-      const TwPair<typename A::word> t = in_n ? tw[idx + (1 << (l1 + LOGS))] : tw[idx];
-      if (out_p) zw[k] = t;
-      const bool xc = NTTMUL_FIRST_XC && g == 0 && l == 0 && l1 == 0;
-#define NTTMUL_CT_T(IN, OUT, XC_)                                 \
-  do {                                                            \
-    ar.template ct_t<IN, OUT, XC_>(x[k], x[k + dist], t.w, t.ws); \
-    if (NPOLY == 2) ar.template ct_t<IN, OUT, XC_>(y[k], y[k + dist], t.w, t.ws); \
-  } while (0)
-      if (xc) {
-        if (out_p) NTTMUL_CT_T(false, true, true); else NTTMUL_CT_T(false, false, true);
-      } else if (in_n) {
-        if (out_p) NTTMUL_CT_T(true, true, false); else NTTMUL_CT_T(true, false, false);
-      } else {
-        if (out_p) NTTMUL_CT_T(false, true, false); else NTTMUL_CT_T(false, false, false);
-      }
-#undef NTTMUL_CT_T
-      continue;
-    }
     const TwPair<typename A::word> t = NTTMUL_HOOK_TW(tw, idx, 0);
     if (l == S - SKIP - 1) zw[k] = t;
-    if constexpr (kTypedP<A>()) {
-      // Arith32P: register k was written as a (signed) difference by the previous stage iff
-      // bit 2 dist is set; this stage leaves its difference in k + dist signed iff the next
-      // stage of the group uses that register as an X (bit dist / 2 clear).  kWT: the first
-      // stage of groups 1 and 2 reads the type TIN of the wave
-      constexpr bool kWt = kWT<A, LOGS>();
-      const bool xn = l > 0 ? (k & (2 * dist)) != 0 : (kWt && g > 0 && TIN);
-      // (P_TYPED 2: the last stage before the base multiplication leaves its differences
-      // signed as well; Arith32P::basemul corrects the -w blocks with the carry of x + q; kWT:
-      // so does the last stage before an exchange)
-      const bool yn = (NTTMUL_P_TYPED >= 2
-                           ? l < S - SKIP - 1 || (SKIP > 0 && g + 1 == Gr::G) ||
-                                 (kWt && g + 1 < Gr::G)
-                           : l < S - SKIP - 1 && !((k + dist) & (dist >> 1)));
-      const bool xc = NTTMUL_FIRST_XC && g == 0 && l == 0 && l1 == 0;
-      constexpr bool kAsm = kWt && g > 0 && TIN;  // see Arith32P::pmul_s
+    // global stage 0 of a whole polynomial reads canonical input (the API contract, [0, q)):
+    // its X operands need no reduction
+    const bool xc = g == 0 && l == 0 && l1 == 0;
+    if constexpr (IsPlantard<A>::value) {
+      // Arith32P: register k was written as a (signed) difference by the previous stage of the
+      // group iff bit 2 dist is set; this stage leaves its differences signed unless it is the
+      // group's last before an exchange (the last stage before the base multiplication leaves
+      // them signed as well: Arith32P::basemul corrects the -w blocks with the carry of x + q)
+      const bool xn = l > 0 && (k & (2 * dist)) != 0;
+      const bool yn = l < S - SKIP - 1 || (SKIP > 0 && g + 1 == Gr::G);
 #define NTTMUL_CT_P(XC_, XN_, YN_)                                         \
   do {                                                                     \
-    ar.template ct<XC_, XN_, YN_, kAsm>(x[k], x[k + dist], t.w, t.ws);      \
-    if (NPOLY == 2) ar.template ct<XC_, XN_, YN_, kAsm>(y[k], y[k + dist], t.w, t.ws); \
+    ar.template ct<XC_, XN_, YN_>(x[k], x[k + dist], t.w, t.ws);            \
+    if (NPOLY == 2) ar.template ct<XC_, XN_, YN_>(y[k], y[k + dist], t.w, t.ws); \
   } while (0)
       if (xc) {
         if (yn) NTTMUL_CT_P(true, false, true); else NTTMUL_CT_P(true, false, false);
@@ -444,9 +304,7 @@ __device__ __forceinline__ void fwd_stage(const A &ar, typename A::word (&x)[16]
 #undef NTTMUL_CT_P
       continue;
     }
-    // global stage 0 of a whole polynomial reads canonical input (the API contract, [0, q)):
-    // its X operands need no reduction
-    if (NTTMUL_FIRST_XC && g == 0 && l == 0 && l1 == 0) {
+    if (xc) {
       ar.template ct<true>(x[k], x[k + dist], t.w, t.ws);
       if (NPOLY == 2) ar.template ct<true>(y[k], y[k + dist], t.w, t.ws);
     } else {
@@ -465,7 +323,7 @@ __device__ __forceinline__ void fwd_group(const A &ar, typename A::word (&x)[16]
                                           const TwPair<typename A::word> *__restrict__ tw, int j,
                                           int row, int l1,
                                           TwPair<typename A::word> (&zw)[16]) {
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int S = Gr::S(g);
   if constexpr (sizeof(typename A::word) == 8) {
     // 64-bit words: stages by compile-time recursion.  The loop body exceeds the unroller's
@@ -474,21 +332,13 @@ __device__ __forceinline__ void fwd_group(const A &ar, typename A::word (&x)[16]
     // 32-bit kernels unroll either way; the recursion reorders them for +0.2-0.8 %, so they keep
     // the loop.)
     if constexpr (L < S - SKIP) {
-      fwd_stage<A, LOGS, g, NPOLY, SKIP, 0>(ar, x, y, tw, j, row, l1, zw, L);
+      fwd_stage<A, LOGS, g, NPOLY, SKIP>(ar, x, y, tw, j, row, l1, zw, L);
       fwd_group<A, LOGS, g, NPOLY, SKIP, L + 1>(ar, x, y, tw, j, row, l1, zw);
     }
   } else {
 #pragma unroll
-    for (int l = 0; l < S - SKIP; l++) {
-      if (kWT<A, LOGS>() && g > 0 && l == 0) {  // one wave-uniform branch per group
-        if (Gr::wave_type(j))
-          fwd_stage<A, LOGS, g, NPOLY, SKIP, 1>(ar, x, y, tw, j, row, l1, zw, l);
-        else
-          fwd_stage<A, LOGS, g, NPOLY, SKIP, 0>(ar, x, y, tw, j, row, l1, zw, l);
-      } else {
-        fwd_stage<A, LOGS, g, NPOLY, SKIP, 0>(ar, x, y, tw, j, row, l1, zw, l);
-      }
-    }
+    for (int l = 0; l < S - SKIP; l++)
+      fwd_stage<A, LOGS, g, NPOLY, SKIP>(ar, x, y, tw, j, row, l1, zw, l);
   }
 }
 
@@ -498,7 +348,7 @@ template <class A, int LOGS, int g, bool SCALE, int SKIP>
 __device__ __forceinline__ void inv_stage(const KParams<A> &P, typename A::word (&x)[16],
                                           const TwPair<typename A::word> *__restrict__ tw, int j,
                                           int row, int l1, int l) {
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int S = Gr::S(g), st0 = Gr::ST0(g), ns = Gr::NS(g);
   const int dist = 8 >> l;
   const int st = st0 + l;
@@ -506,30 +356,6 @@ __device__ __forceinline__ void inv_stage(const KParams<A> &P, typename A::word 
 #pragma unroll
   for (int k = 0; k < 16; k++) {
     if (k & dist) continue;
-    if constexpr (A::kTyped) {
-      // first stage of the group (inverse order) reads P-type; later ones read the previous
-      // stage's Y registers (bit dist / 2 of k) as N-type; the group's last stage writes P-type
-      const bool in_n = l < S - 1 - SKIP && (k & (dist >> 1));
-      const bool out_p = l == 0;
-      if (SCALE && st == 0) {
-        if (in_n)
-          P.ar.template gs_scaled_t<true>(x[k], x[k + dist], P.f, P.fs, P.wf, P.wfs);
-        else
-          P.ar.template gs_scaled_t<false>(x[k], x[k + dist], P.f, P.fs, P.wf, P.wfs);
-        continue;
-      }
-      const int m = k / ns;
-      const int idx = tbase + (Gr::blk(g, j, k) << l) + (m >> (S - l));
-      const TwPair<typename A::word> t = out_p ? tw[idx] : tw[idx + (1 << (l1 + LOGS))];
-      if (in_n) {
-        if (out_p) P.ar.template gs_t<true, true>(x[k], x[k + dist], t.w, t.ws);
-        else P.ar.template gs_t<true, false>(x[k], x[k + dist], t.w, t.ws);
-      } else {
-        if (out_p) P.ar.template gs_t<false, true>(x[k], x[k + dist], t.w, t.ws);
-        else P.ar.template gs_t<false, false>(x[k], x[k + dist], t.w, t.ws);
-      }
-      continue;
-    }
     if (SCALE && st == 0) {
       P.ar.gs_scaled(x[k], x[k + dist], P.f, P.fs, P.wf, P.wfs);
     } else {
@@ -572,58 +398,45 @@ __device__ __forceinline__ void xsync() {
 }
 
 
-// Move 16 registers of each region from layout gfrom to layout gto through LDS.  ES: LDS words
-// between consecutive (padded) elements of one polynomial (1; k_cols8 interleaves the 16 column
-// transforms of a workgroup element by element, ES = 16, so a wave's lanes on adjacent columns
-// touch adjacent words).
-template <int LOGS, int gfrom, int gto, int NREG, class W, int SYNC = 0, bool WT = false, int ES = 1>
-__device__ __forceinline__ void exchange(W (&x)[16], W (&y)[16], W *lds_x, W *lds_y, int j) {
-  using Gr = Groups<LOGS, WT>;
+// Move 16 registers of NREG (1 or 2) polynomials from layout gfrom to layout gto through one LDS
+// region, the two polynomials in turn (half the LDS of exchanging them together: 7 blocks per CU
+// instead of 4 at n = 4096).  ES: LDS words between consecutive (padded) elements of one
+// polynomial (1; k_cols8 interleaves the 16 column transforms of a workgroup element by element,
+// ES = 16, so a wave's lanes on adjacent columns touch adjacent words).
+template <int LOGS, int gfrom, int gto, int NREG, class W, int SYNC = 0, int ES = 1>
+__device__ __forceinline__ void exchange(W (&x)[16], W (&y)[16], W *lds, int j) {
+  using Gr = Groups<LOGS>;
   NTTMUL_HOOK_XCHG();
   constexpr int X = gfrom < gto ? gfrom : gto;
   const int bw = Gr::template padx<X>(Gr::base(gfrom, j)) * ES;
   const int br = Gr::template padx<X>(Gr::base(gto, j)) * ES;
-  if (lds_regions<W>() == 1 && NREG == 2) {  // one region, the two polynomials in turn
 #pragma unroll
-    for (int k = 0; k < 16; k++) lds_x[bw + Gr::template padx<X>(Gr::off(gfrom, k)) * ES] = x[k];
-    xsync<SYNC>();
-#pragma unroll
-    for (int k = 0; k < 16; k++) x[k] = lds_x[br + Gr::template padx<X>(Gr::off(gto, k)) * ES];
-    xsync<SYNC>();
-#pragma unroll
-    for (int k = 0; k < 16; k++) lds_x[bw + Gr::template padx<X>(Gr::off(gfrom, k)) * ES] = y[k];
-    xsync<SYNC>();
-#pragma unroll
-    for (int k = 0; k < 16; k++) y[k] = lds_x[br + Gr::template padx<X>(Gr::off(gto, k)) * ES];
-    xsync<SYNC>();
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    lds_x[bw + Gr::template padx<X>(Gr::off(gfrom, k)) * ES] = x[k];
-    if (NREG == 2) lds_y[bw + Gr::template padx<X>(Gr::off(gfrom, k)) * ES] = y[k];
-  }
+  for (int k = 0; k < 16; k++) lds[bw + Gr::template padx<X>(Gr::off(gfrom, k)) * ES] = x[k];
   xsync<SYNC>();
 #pragma unroll
-  for (int k = 0; k < 16; k++) {
-    x[k] = lds_x[br + Gr::template padx<X>(Gr::off(gto, k)) * ES];
-    if (NREG == 2) y[k] = lds_y[br + Gr::template padx<X>(Gr::off(gto, k)) * ES];
-  }
+  for (int k = 0; k < 16; k++) x[k] = lds[br + Gr::template padx<X>(Gr::off(gto, k)) * ES];
   xsync<SYNC>();
+  if constexpr (NREG == 2) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) lds[bw + Gr::template padx<X>(Gr::off(gfrom, k)) * ES] = y[k];
+    xsync<SYNC>();
+#pragma unroll
+    for (int k = 0; k < 16; k++) y[k] = lds[br + Gr::template padx<X>(Gr::off(gto, k)) * ES];
+    xsync<SYNC>();
+  }
 }
 
 template <class A, int LOGS, int g, int NPOLY = 2, int SKIP = 0, int SYNC = 0, int ES = 1>
 __device__ __forceinline__ void fwd_all(const A &ar, typename A::word (&x)[16],
-                                        typename A::word (&y)[16], typename A::word *lx,
-                                        typename A::word *ly,
+                                        typename A::word (&y)[16], typename A::word *lds,
                                         const TwPair<typename A::word> *__restrict__ tw, int j,
                                         int row, int l1, TwPair<typename A::word> (&zw)[16]) {
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr bool last = g + 1 == Gr::G;
   fwd_group<A, LOGS, g, NPOLY, last ? SKIP : 0>(ar, x, y, tw, j, row, l1, zw);
   if constexpr (!last) {
-    exchange<LOGS, g, g + 1, NPOLY, typename A::word, SYNC, kWT<A, LOGS>(), ES>(x, y, lx, ly, j);
-    fwd_all<A, LOGS, g + 1, NPOLY, SKIP, SYNC, ES>(ar, x, y, lx, ly, tw, j, row, l1, zw);
+    exchange<LOGS, g, g + 1, NPOLY, typename A::word, SYNC, ES>(x, y, lds, j);
+    fwd_all<A, LOGS, g + 1, NPOLY, SKIP, SYNC, ES>(ar, x, y, lds, tw, j, row, l1, zw);
   }
 }
 
@@ -632,16 +445,15 @@ __device__ __forceinline__ void fwd_all(const A &ar, typename A::word (&x)[16],
 template <class A, int LOGS, int g, bool SCALE, int SKIP = 0, int SYNC = 0, int NPOLY = 1,
           int ES = 1>
 __device__ __forceinline__ void inv_all(const KParams<A> &P, typename A::word (&x)[16],
-                                        typename A::word (&y)[16], typename A::word *lx,
-                                        typename A::word *ly,
+                                        typename A::word (&y)[16], typename A::word *lds,
                                         const TwPair<typename A::word> *__restrict__ tw, int j,
                                         int row, int l1) {
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   inv_group<A, LOGS, g, SCALE, g + 1 == Gr::G ? SKIP : 0>(P, x, tw, j, row, l1);
   if constexpr (NPOLY == 2) inv_group<A, LOGS, g, SCALE, g + 1 == Gr::G ? SKIP : 0>(P, y, tw, j, row, l1);
   if constexpr (g > 0) {
-    exchange<LOGS, g, g - 1, NPOLY, typename A::word, SYNC, kWT<A, LOGS>(), ES>(x, y, lx, ly, j);
-    inv_all<A, LOGS, g - 1, SCALE, SKIP, SYNC, NPOLY, ES>(P, x, y, lx, ly, tw, j, row, l1);
+    exchange<LOGS, g, g - 1, NPOLY, typename A::word, SYNC, ES>(x, y, lds, j);
+    inv_all<A, LOGS, g - 1, SCALE, SKIP, SYNC, NPOLY, ES>(P, x, y, lds, tw, j, row, l1);
   }
 }
 
@@ -654,15 +466,15 @@ __device__ __forceinline__ void inv_all(const KParams<A> &P, typename A::word (&
 // offset says X or Y.  Same canonical output as the full transform (the product is unique).
 //
 // base_mult_rec: the same with the blocks by compile-time recursion over the register index K0
-// instead of an unrolled loop, for Arith32P3 (NTTMUL_P3_PIN; base_mult below dispatches to it):
+// instead of an unrolled loop, for Arith32P3 (base_mult below dispatches to it):
 // its base multiplication pins the halfway fold with an empty asm, and a loop holding inline asm
 // is not fully unrolled (its register indices turn into runtime ones).  The other classes keep
 // the loop (for them the recursion only reorders the code: +15 VALU in the C5 row pass).
 template <class A, int LOGS, int D, int K0 = 0>
 __device__ __forceinline__ void base_mult_rec(const A &ar, typename A::word (&x)[16],
                                           const typename A::word (&y)[16],
-                                          const TwPair<typename A::word> (&zw)[16], int j) {
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+                                          const TwPair<typename A::word> (&zw)[16]) {
+  using Gr = Groups<LOGS>;
   constexpr int g = Gr::G - 1, B = 1 << D;
   static_assert(D > 0 && Gr::S(g) > D, "base blocks of 2^D > 1 coefficients in the last group");
   if constexpr (K0 < 16) {
@@ -673,21 +485,11 @@ __device__ __forceinline__ void base_mult_rec(const A &ar, typename A::word (&x)
       for (int i = 0; i < B; i++) r[i] = Gr::reg_of(g, o0 + i);
       constexpr bool neg = (o0 >> D) & 1;
       constexpr int kz = Gr::reg_of(g, o0 & ~B);
-      TwPair<typename A::word> z = zw[kz];
-      // typed arithmetic: the last forward stage (dist 8 >> (S - D - 1)) multiplied N-type
-      // operands, and so kept the centred twiddle, when bit 2 dist of its X register is set
+      const TwPair<typename A::word> z = zw[kz];
+      // Arith32P: the last forward stage (dist 8 >> (S - D - 1)) multiplied signed differences,
+      // and so kept the pair in signed form, when bit 2 dist of its X register is set
       constexpr int dl = 8 >> (Gr::S(g) - D - 1);
-      // (Arith32P, NTTMUL_P_TYPED 2: the same condition says the pair is in signed form)
-      constexpr bool typed_z = A::kTyped || (kTypedP<A>() && NTTMUL_P_TYPED >= 2);
-      // (kWT, when that stage was its group's first: the pair is in signed form exactly when the
-      // wave's elements were the previous group's differences.  The signed-input product is
-      // exact for canonical inputs too, so every wave takes it: the unsigned pair of the other
-      // waves becomes the signed one by b1 + (b0 >> 31), two instructions, instead of a second
-      // copy of the base multiplication behind a branch)
-      constexpr bool kWtFirst = kWT<A, LOGS>() && Gr::S(g) - D - 1 == 0;
-      if constexpr (kWtFirst)
-        z.ws += (typename A::word)((z.w >> 31) & (1 - Gr::wave_type(j)));
-      constexpr bool zc = typed_z && (kWtFirst || (Gr::S(g) - D - 1 > 0 && (kz & (2 * dl))));
+      constexpr bool zc = IsPlantard<A>::value && Gr::S(g) - D - 1 > 0 && (kz & (2 * dl));
       typename A::word a[B], b[B];
 #pragma unroll
       for (int i = 0; i < B; i++) a[i] = x[r[i]], b[i] = y[r[i]];
@@ -695,22 +497,22 @@ __device__ __forceinline__ void base_mult_rec(const A &ar, typename A::word (&x)
 #pragma unroll
       for (int i = 0; i < B; i++) x[r[i]] = a[i];
     }
-    base_mult_rec<A, LOGS, D, K0 + 1>(ar, x, y, zw, j);
+    base_mult_rec<A, LOGS, D, K0 + 1>(ar, x, y, zw);
   }
 }
 
 template <class A, int LOGS, int D>
 __device__ __forceinline__ void base_mult(const A &ar, typename A::word (&x)[16],
                                           const typename A::word (&y)[16],
-                                          const TwPair<typename A::word> (&zw)[16], int j) {
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+                                          const TwPair<typename A::word> (&zw)[16]) {
+  using Gr = Groups<LOGS>;
   constexpr int g = Gr::G - 1, B = 1 << D;
   static_assert(D == 0 || Gr::S(g) > D, "last register group too short for the base blocks");
   if constexpr (D == 0) {
 #pragma unroll
     for (int k = 0; k < 16; k++) x[k] = ar.mont(x[k], y[k]);
-  } else if constexpr (std::is_same<A, Arith32P3>::value && NTTMUL_P3_PIN) {
-    base_mult_rec<A, LOGS, D>(ar, x, y, zw, j);
+  } else if constexpr (std::is_same<A, Arith32P3>::value) {
+    base_mult_rec<A, LOGS, D>(ar, x, y, zw);
   } else {
 #pragma unroll
     for (int k0 = 0; k0 < 16; k0++) {
@@ -721,21 +523,11 @@ __device__ __forceinline__ void base_mult(const A &ar, typename A::word (&x)[16]
       for (int i = 0; i < B; i++) r[i] = Gr::reg_of(g, o0 + i);
       const bool neg = (o0 >> D) & 1;
       const int kz = Gr::reg_of(g, o0 & ~B);
-      TwPair<typename A::word> z = zw[kz];
-      // typed arithmetic: the last forward stage (dist 8 >> (S - D - 1)) multiplied N-type
-      // operands, and so kept the centred twiddle, when bit 2 dist of its X register is set
+      const TwPair<typename A::word> z = zw[kz];
+      // Arith32P: the last forward stage (dist 8 >> (S - D - 1)) multiplied signed differences,
+      // and so kept the pair in signed form, when bit 2 dist of its X register is set
       constexpr int dl = 8 >> (Gr::S(g) - D - 1);
-      // (Arith32P, NTTMUL_P_TYPED 2: the same condition says the pair is in signed form)
-      constexpr bool typed_z = A::kTyped || (kTypedP<A>() && NTTMUL_P_TYPED >= 2);
-      // (kWT, when that stage was its group's first: the pair is in signed form exactly when the
-      // wave's elements were the previous group's differences.  The signed-input product is
-      // exact for canonical inputs too, so every wave takes it: the unsigned pair of the other
-      // waves becomes the signed one by b1 + (b0 >> 31), two instructions, instead of a second
-      // copy of the base multiplication behind a branch)
-      constexpr bool kWtFirst = kWT<A, LOGS>() && Gr::S(g) - D - 1 == 0;
-      if constexpr (kWtFirst)
-        z.ws += (typename A::word)((z.w >> 31) & (1 - Gr::wave_type(j)));
-      const bool zc = typed_z && (kWtFirst || (Gr::S(g) - D - 1 > 0 && (kz & (2 * dl))));
+      const bool zc = IsPlantard<A>::value && Gr::S(g) - D - 1 > 0 && (kz & (2 * dl));
       typename A::word a[B], b[B];
 #pragma unroll
       for (int i = 0; i < B; i++) a[i] = x[r[i]], b[i] = y[r[i]];
@@ -755,35 +547,14 @@ __device__ __forceinline__ void base_mult(const A &ar, typename A::word (&x)[16]
 }
 
 // Threads per k_rows workgroup: 256 (one n = 4096 product, or 256 / (n / 16) smaller ones),
-// except one wave per workgroup at n = 1024 (NTTMUL_SMALL_BLOCK): one product per wave, so no
-// barrier ties four independent products together.  C2 (n = 1024 x 4096) 22.2 -> 21.6 us,
-// n = 1024 x 262144 -1 %; n = 256 one wave per 4 products was not faster (profiles/r2)
-#ifndef NTTMUL_SMALL_BLOCK
-#define NTTMUL_SMALL_BLOCK 1
-#endif
-__host__ __device__ constexpr int rows_threads(int logs) {
-  return NTTMUL_SMALL_BLOCK && logs == 10 ? 64 : 256;
-}
-// __launch_bounds__ minimum waves per SIMD of k_rows: NTTMUL_MIN_WAVES, and for the one-wave
-// n = 1024 products NTTMUL_MIN_WAVES_1024 (an A/B switch: 8 gives 64 VGPRs instead of 84-86, so
-// the next C2 launch's four waves per SIMD fit beside the running four on another stream, but
-// measured +3.2 % on one stream and +3.6 % on two; default: no bound)
-#ifndef NTTMUL_MIN_WAVES_1024
-#define NTTMUL_MIN_WAVES_1024 NTTMUL_MIN_WAVES
-#endif
-__host__ __device__ constexpr int rows_min_waves(int logs) {
-  return NTTMUL_SMALL_BLOCK && logs == 10 ? NTTMUL_MIN_WAVES_1024 : NTTMUL_MIN_WAVES;
-}
-// Square split (k_cols8): the intermediates ta, tb, tc tiled per 16 columns (NTTMUL_C5_TILE), so
-// the column passes store / load one contiguous 32 KiB tile per workgroup and the row pass moves
-// 512 contiguous bytes per instruction, instead of 128-byte runs 2 KiB apart (a row-major
-// column) on the column side
-#ifndef NTTMUL_C5_TILE
-#define NTTMUL_C5_TILE 1
-#endif
-__host__ __device__ constexpr bool c8_tile(int logs, int l1) {
-  return NTTMUL_C5_TILE && logs == 8 && l1 == 8;
-}
+// except one wave per workgroup at n = 1024: one product per wave, so no barrier ties four
+// independent products together
+__host__ __device__ constexpr int rows_threads(int logs) { return logs == 10 ? 64 : 256; }
+// Square split (k_cols8): the intermediates ta, tb, tc are tiled per 16 columns, so the column
+// passes store / load one contiguous 32 KiB tile per workgroup and the row pass moves 512
+// contiguous bytes per instruction, instead of 128-byte runs 2 KiB apart (a row-major column) on
+// the column side
+__host__ __device__ constexpr bool c8_tile(int logs, int l1) { return logs == 8 && l1 == 8; }
 
 // Fused product of `units` independent rows of 2^LOGS coefficients.
 //   L1 == 0 : each unit is a whole polynomial (n = 2^LOGS): full product, canonical output.
@@ -819,14 +590,17 @@ __device__ __forceinline__ void clk_stamp(int k) {
 #endif
 
 template <class A, class TIn, class TOut, int LOGS, int L1, bool PRIO = false>
-__global__ __launch_bounds__(rows_threads(LOGS), rows_min_waves(LOGS)) void k_rows(
+__global__ __launch_bounds__(rows_threads(LOGS)) void k_rows(
     KParams<A> P, const TIn *__restrict__ a, const TIn *__restrict__ b, TOut *__restrict__ c,
     size_t units) {
   using W = typename A::word;
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int N = Gr::N, TP = N / 16, PB = rows_threads(LOGS) / TP, G = Gr::G, NP = Gr::NP;
-  constexpr bool kNT = NTTMUL_NT && (L1 == 0 || NTTMUL_NT_MP);
-  __shared__ W lds[PB][lds_regions<W>()][NP];
+  // coefficient streams are touched once per product: non-temporal.  The row pass of a
+  // multi-pass product (L1 > 0) reads and writes intermediates that the column passes touch again
+  // and keeps them temporal, so a sub-batch whose scratch fits the Infinity Cache can stay there
+  constexpr bool kNT = L1 == 0;
+  __shared__ W lds[PB][NP];
 
   const int pb = threadIdx.x / TP, j = threadIdx.x % TP;
   const size_t u = (size_t)blockIdx.x * PB + pb;
@@ -843,48 +617,30 @@ __global__ __launch_bounds__(rows_threads(LOGS), rows_min_waves(LOGS)) void k_ro
   const size_t base_l = live ? base_g : (size_t)Gr::base(0, j);
   const size_t base_r = NTTMUL_HOOK_ROWS_LD(base_l, u, N, Gr::base(0, j));
 
-  // NTTMUL_C5_BUF, the square split's row pass: one descriptor per polynomial (its 16 rows per
-  // block share it), 32-bit lane offsets, each register's constant offset in the scalar offset
-  constexpr bool kRowBuf = kTile && NTTMUL_C5_BUF && !NTTMUL_ROWS_HOOKED && sizeof(W) == 8 &&
-                           sizeof(TIn) == 8 && sizeof(TOut) == 8 && !kNT;
+  // the square split's row pass: one descriptor per polynomial (its 16 rows per block share it),
+  // 32-bit lane offsets, each register's constant offset in the scalar offset
+  constexpr bool kRowBuf = kTile && !NTTMUL_ROWS_HOOKED && sizeof(W) == 8 && sizeof(TIn) == 8 &&
+                           sizeof(TOut) == 8;
   const size_t rpoly = (((size_t)blockIdx.x * PB) >> 8) << 16;  // block-uniform
   const int rlane = (int)(((u & 255) << 4) + Gr::base(0, j));
   CLK_STAMP(0);
   if constexpr (PRIO) NTTMUL_HOOK_PRIO0(u);  // rows_prio
   W x[16], y[16];
-  // NTTMUL_CPOL >= 0: a, b, c of a one-product-per-block u32 product through buffer loads /
-  // stores (descriptor from block-uniform values, 32-bit per-lane offsets, nt by default)
-  // (64-bit words of the square split take kRowBuf below: one descriptor per polynomial and the
-  // constant offsets in the scalar offset; round 2's form, an offset per register, measured
-  // +0.8 % at C5 with its row pass at 131 VGPRs instead of 126)
-  constexpr bool kCpol = NTTMUL_CPOL >= 0 && PB == 1 && L1 == 0 && sizeof(W) == 4 &&
-                         sizeof(TIn) == 4 && sizeof(TOut) == 4;
-  constexpr int kAux = NTTMUL_CPOL < 0 ? 0 : NTTMUL_CPOL;
-  constexpr int kAuxSt = NTTMUL_CPOL_ST < 0 ? 0 : NTTMUL_CPOL_ST;
-  // n = 1024 one-wave products (C2: a single generation of waves that all wait for their loads):
-  // a's forward transform runs while b is still landing (NTTMUL_SPLIT_AB)
-  constexpr bool kSplitAB = NTTMUL_SPLIT_AB && kCpol && LOGS == 10;
+  // a, b, c of a one-product-per-block u32 product (n = 4096, 1024) through buffer loads / stores
+  // on a block-uniform descriptor with nt cache policy: the 32-bit offsets drop the 64-bit address
+  // adds of global nt loads.  The per-lane offset is the thread's base alone; each register's
+  // constant part rides in the instruction's scalar offset, so no VALU add forms its address.
+  // (64-bit words of the square split take kRowBuf below)
+  constexpr bool kCpol = PB == 1 && L1 == 0 && sizeof(W) == 4 && sizeof(TIn) == 4 &&
+                         sizeof(TOut) == 4;
   if constexpr (kCpol) {
     const size_t ub = live ? (size_t)blockIdx.x : 0;
     const auto ra = span_rsrc(a + ub * N, N), rb = span_rsrc(b + ub * N, N);
-    if constexpr (kSplitAB) {  // all of a first: a's transform starts before b has landed
 #pragma unroll
-      for (int k = 0; k < 16; k++) x[k] = (W)buf_ld32<kAux>(ra, (Gr::base(0, j) + Gr::off(0, k)) * 4);
-#pragma unroll
-      for (int k = 0; k < 16; k++) y[k] = (W)buf_ld32<kAux>(rb, (Gr::base(0, j) + Gr::off(0, k)) * 4);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        if constexpr (NTTMUL_BUF_SOFF) {
-          const int vo = Gr::base(0, j) * 4, so = Gr::off(0, k) * 4;
-          x[k] = (W)buf_ld32<kAux>(ra, vo, so);
-          y[k] = (W)buf_ld32<kAux>(rb, vo, so);
-        } else {
-          const int off = (Gr::base(0, j) + Gr::off(0, k)) * 4;
-          x[k] = (W)buf_ld32<kAux>(ra, off);
-          y[k] = (W)buf_ld32<kAux>(rb, off);
-        }
-      }
+    for (int k = 0; k < 16; k++) {
+      const int vo = Gr::base(0, j) * 4, so = Gr::off(0, k) * 4;
+      x[k] = (W)buf_ld32<kAuxNt>(ra, vo, so);
+      y[k] = (W)buf_ld32<kAuxNt>(rb, vo, so);
     }
   } else if constexpr (kRowBuf) {
     // (units is a multiple of 256 rows here, so every row of the block is live)
@@ -903,19 +659,14 @@ __global__ __launch_bounds__(rows_threads(LOGS), rows_min_waves(LOGS)) void k_ro
     }
   }
   NTTMUL_HOOK_ROWS_INPUT(x, y, u, j);
-  W *lx = lds[pb][0], *ly = lds[pb][lds_regions<W>() - 1];
-  constexpr int D = NTTMUL_BASE_D ? A::kBaseD : 0;
+  W *lx = lds[pb];
+  constexpr int D = A::kBaseD;
   TwPair<W> zw[16];
-  if constexpr (kSplitAB) {  // a's forward transform, then b's (each waits only for its loads)
-    fwd_all<A, LOGS, 0, 1, D>(P.ar, x, y, lx, ly, P.fw, j, row, L1, zw);
-    fwd_all<A, LOGS, 0, 1, D>(P.ar, y, x, lx, ly, P.fw, j, row, L1, zw);
-  } else {
-    fwd_all<A, LOGS, 0, 2, D>(P.ar, x, y, lx, ly, P.fw, j, row, L1, zw);
-  }
+  fwd_all<A, LOGS, 0, 2, D>(P.ar, x, y, lx, P.fw, j, row, L1, zw);
   if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-  base_mult<A, LOGS, D>(P.ar, x, y, zw, j);
+  base_mult<A, LOGS, D>(P.ar, x, y, zw);
   if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-  inv_all<A, LOGS, G - 1, L1 == 0, D>(P, x, y, lx, ly, P.iw, j, row, L1);
+  inv_all<A, LOGS, G - 1, L1 == 0, D>(P, x, y, lx, P.iw, j, row, L1);
   NTTMUL_HOOK_ROWS_OUTPUT(x, c, base_g, live);
   if constexpr (kCpol) {
     if (live) {
@@ -924,10 +675,7 @@ __global__ __launch_bounds__(rows_threads(LOGS), rows_min_waves(LOGS)) void k_ro
       for (int k = 0; k < 16; k++) {
         W v = x[k];
         if (!A::kInvCanonical) v = P.ar.canon_inv(v);
-        if constexpr (NTTMUL_BUF_SOFF)
-          buf_st32<kAuxSt>(rc, Gr::base(0, j) * 4, (uint32_t)v, Gr::off(0, k) * 4);
-        else
-          buf_st32<kAuxSt>(rc, (Gr::base(0, j) + Gr::off(0, k)) * 4, (uint32_t)v);
+        buf_st32<kAuxNt>(rc, Gr::base(0, j) * 4, (uint32_t)v, Gr::off(0, k) * 4);
       }
     }
     CLK_STAMP(1);
@@ -953,9 +701,7 @@ __global__ __launch_bounds__(rows_threads(LOGS), rows_min_waves(LOGS)) void k_ro
 }
 
 // s_sleep argument between the device server's polls (x 64 cycles: 2 = 53 ns at 2.4 GHz)
-#ifndef NTTMUL_SERVER_POLL_SLEEP
-#define NTTMUL_SERVER_POLL_SLEEP 2
-#endif
+constexpr int kServerPollSleep = 2;
 // The wide single-product path of the device server (n = 256, one product: every call of the
 // reference's ntt256_product4 / product1 shims).  The one-wave path gives a product 16 lanes of
 // 16 coefficients (a and b on two lane groups, the inverse on one), so a call is about 1,100
@@ -964,7 +710,7 @@ __global__ __launch_bounds__(rows_threads(LOGS), rows_min_waves(LOGS)) void k_ro
 // multiplication and the inverse, about 3x fewer instructions on the critical path for 7 LDS
 // exchanges instead of 2.  Register groups of two stages: layout P holds element bits P, P + 1 in
 // the four registers, e = (t mod 2^P) | (t >> P) << (P + 2) | i << P for lane t, register i.
-// Types as in the fused product (Arith32P, NTTMUL_P_TYPED 2), with the planner's twiddle table
+// Types as in the fused product (Arith32P), with the planner's twiddle table
 // re-typed per entry in LDS (fu: every pair unsigned, fs: every pair signed) because the group
 // boundaries differ: the second stage of a group multiplies the first stage's differences as
 // signed values with signed pairs (odd entries), the first reads unsigned lazy values, and the
@@ -1108,10 +854,10 @@ __global__ __launch_bounds__(LOGS == 8 ? 512 : LOGS == 9 ? 64 : 128) void k_serv
     KParams<A> P, const ServerReq *req, ServerBox *box, unsigned tw_pairs,
     unsigned long long idle_ticks, unsigned long long life_ticks) {
   using W = typename A::word;
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int N = Gr::N, TP = N / 16, PB = 64 / TP, G = Gr::G, NP = Gr::NP;
   static_assert(sizeof(W) == 4 && TP <= 64, "u32 words, n <= 1024");
-  constexpr bool kWide = LOGS == 8 && IsPlantard<A>::value && NTTMUL_BASE_D && A::kBaseD == 2;
+  constexpr bool kWide = LOGS == 8 && IsPlantard<A>::value && A::kBaseD == 2;
   constexpr bool kPair = LOGS == 10;  // n = 1024 (one product per request): a and b on two waves
   constexpr int KW = ServerBox::kWords, NT = LOGS == 8 ? 512 : LOGS == 9 ? 64 : 128;
   __shared__ W lds[kWide ? 2 * PB : PB < 2 ? 2 : PB][NP];
@@ -1134,7 +880,7 @@ __global__ __launch_bounds__(LOGS == 8 ? 512 : LOGS == 9 ? 64 : 128) void k_serv
   P.fw = twf;
   P.iw = twi;
   W *lx = lds[pb];
-  constexpr int D = NTTMUL_BASE_D ? A::kBaseD : 0;
+  constexpr int D = A::kBaseD;
   unsigned seen = __hip_atomic_load(&box->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   seen = __builtin_amdgcn_readfirstlane(seen);
   __syncthreads();  // the twiddles in LDS before the first transform
@@ -1142,11 +888,10 @@ __global__ __launch_bounds__(LOGS == 8 ? 512 : LOGS == 9 ? 64 : 128) void k_serv
   if constexpr (kWide) wtw = wide_tw(wfu, wfs, twi, lane);
   const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
   unsigned long long last = t0;
-  // one poll at a time, NTTMUL_SERVER_POLL_SLEEP apart.  (Rounds 4b-4f kept three polls in
-  // flight 16 x 64 cycles apart, sized for reads across PCIe; with the request in device memory a
-  // single poll is 1 us faster per request, and with it in host memory too:
-  // tools/microbench/mailbox_latency.hip, profiles/r4/mailbox/)
-  constexpr int kSleep = NTTMUL_SERVER_POLL_SLEEP;
+  // one poll at a time, kServerPollSleep apart.  (Three polls in flight 16 x 64 cycles apart,
+  // sized for reads across PCIe, were 1 us slower per request with the request in device memory,
+  // and with it in host memory too: tools/microbench/mailbox_latency.hip, profiles/r4/mailbox/)
+  constexpr int kSleep = kServerPollSleep;
   for (;;) {
     unsigned go = seen;
     bool quit = false;
@@ -1255,7 +1000,7 @@ __global__ __launch_bounds__(LOGS == 8 ? 512 : LOGS == 9 ? 64 : 128) void k_serv
 #endif
         TwPair<W> zw[16];
         W *lw = lds[wave];
-        fwd_all<A, LOGS, 0, 1, D, 1>(P.ar, x, y, lw, lw, P.fw, j, 0, 0, zw);
+        fwd_all<A, LOGS, 0, 1, D, 1>(P.ar, x, y, lw, P.fw, j, 0, 0, zw);
         W *hand = (W *)stg[1];  // (b's input, already in wave 1's registers)
         if (wave == 1) {
 #pragma unroll
@@ -1265,8 +1010,8 @@ __global__ __launch_bounds__(LOGS == 8 ? 512 : LOGS == 9 ? 64 : 128) void k_serv
         if (wave == 0) {
 #pragma unroll
           for (int k = 0; k < 16; k++) y[k] = hand[k * 64 + lane];
-          base_mult<A, LOGS, D>(P.ar, x, y, zw, j);
-          inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lw, lw, P.iw, j, 0, 0);
+          base_mult<A, LOGS, D>(P.ar, x, y, zw);
+          inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lw, P.iw, j, 0, 0);
 #ifdef NTTMUL_CLOCK_STAMPS
           __builtin_amdgcn_sched_barrier(0);
           st[2] = __builtin_amdgcn_s_memrealtime();
@@ -1319,15 +1064,15 @@ __global__ __launch_bounds__(LOGS == 8 ? 512 : LOGS == 9 ? 64 : 128) void k_serv
       st[4] = __builtin_amdgcn_s_memtime();
 #endif
       if (split) {
-        fwd_all<A, LOGS, 0, 1, D, 1>(P.ar, x, y, lx, lx, P.fw, j, 0, 0, zw);
+        fwd_all<A, LOGS, 0, 1, D, 1>(P.ar, x, y, lx, P.fw, j, 0, 0, zw);
 #pragma unroll
         for (int k = 0; k < 16; k++)  // group 1's transformed b to group 0's lanes, same j
           y[k] = (W)__builtin_amdgcn_ds_bpermute((lane + TP) << 2, (int)x[k]);
       } else {
-        fwd_all<A, LOGS, 0, 2, D, 1>(P.ar, x, y, lx, lx, P.fw, j, 0, 0, zw);
+        fwd_all<A, LOGS, 0, 2, D, 1>(P.ar, x, y, lx, P.fw, j, 0, 0, zw);
       }
-      base_mult<A, LOGS, D>(P.ar, x, y, zw, j);
-      inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lx, lx, P.iw, j, 0, 0);
+      base_mult<A, LOGS, D>(P.ar, x, y, zw);
+      inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lx, P.iw, j, 0, 0);
 #ifdef NTTMUL_CLOCK_STAMPS
       __builtin_amdgcn_sched_barrier(0);
       st[2] = __builtin_amdgcn_s_memrealtime();
@@ -1390,10 +1135,11 @@ template <class A, class TIn, class TOut, int LOGS, int L1, int DIR>
 __global__ __launch_bounds__(256) void k_xform(KParams<A> P, const TIn *__restrict__ in,
                                                TOut *__restrict__ out, size_t units) {
   using W = typename A::word;
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int N = Gr::N, TP = N / 16, PB = 256 / TP, G = Gr::G, NP = Gr::NP;
   constexpr int GIN = DIR == 0 ? 0 : G - 1, GOUT = DIR == 0 ? G - 1 : 0;
   constexpr int UPG = xform_upg<A, L1, DIR>();
+  // (UPG == 2 uses the first region only: the size is kept, shrinking it changes the descriptor)
   __shared__ W lds[PB][UPG][NP];
   const int pb = threadIdx.x / TP, j = threadIdx.x % TP;
   const size_t u = ((size_t)blockIdx.x * PB + pb) * UPG;
@@ -1418,9 +1164,9 @@ __global__ __launch_bounds__(256) void k_xform(KParams<A> P, const TIn *__restri
   }
   TwPair<W> zw[16];
   if (DIR == 0)
-    fwd_all<A, LOGS, 0, UPG>(P.ar, x, y, lds[pb][0], lds[pb][UPG - 1], P.fw, j, row, L1, zw);
+    fwd_all<A, LOGS, 0, UPG>(P.ar, x, y, lds[pb][0], P.fw, j, row, L1, zw);
   else
-    inv_all<A, LOGS, G - 1, L1 == 0, 0, 0, UPG>(P, x, y, lds[pb][0], lds[pb][UPG - 1], P.iw, j, row, L1);
+    inv_all<A, LOGS, G - 1, L1 == 0, 0, 0, UPG>(P, x, y, lds[pb][0], P.iw, j, row, L1);
   if (live) {
     const size_t base_out = DIR == 1 ? tbase(u, GOUT) : u * N + Gr::base(GOUT, j);
 #pragma unroll
@@ -1480,8 +1226,8 @@ __global__ __launch_bounds__(256) void k_cols_fwd(KParams<A> P, const TIn *__res
   W x[M], y[M];
 #pragma clang loop unroll(full)
   for (int m = 0; m < M; m++) {
-    x[m] = (W)ld_stream<NTTMUL_NT_COLS>(a + base_r + ((size_t)m << logs));
-    y[m] = NPOLY == 2 ? (W)ld_stream<NTTMUL_NT_COLS>(b + base_r + ((size_t)m << logs)) : W(0);
+    x[m] = (W)ld_stream<true>(a + base_r + ((size_t)m << logs));
+    y[m] = NPOLY == 2 ? (W)ld_stream<true>(b + base_r + ((size_t)m << logs)) : W(0);
   }
 #pragma clang loop unroll(full)
   for (int st = 0; st < L1; st++) {
@@ -1496,8 +1242,8 @@ __global__ __launch_bounds__(256) void k_cols_fwd(KParams<A> P, const TIn *__res
   }
 #pragma clang loop unroll(full)
   for (int m = 0; m < M; m++) {
-    st_stream<NTTMUL_NT_COLS>(ta + base_w + ((size_t)m << logs), x[m]);
-    if (NPOLY == 2) st_stream<NTTMUL_NT_COLS>(tb + base_w + ((size_t)m << logs), y[m]);
+    st_stream<true>(ta + base_w + ((size_t)m << logs), x[m]);
+    if (NPOLY == 2) st_stream<true>(tb + base_w + ((size_t)m << logs), y[m]);
   }
 }
 
@@ -1516,7 +1262,7 @@ __global__ __launch_bounds__(256) void k_cols_inv(KParams<A> P,
   const size_t base_r = NTTMUL_HOOK_COLS_LD(base, p, logs + L1, col, 1);
   W x[M];
 #pragma clang loop unroll(full)
-  for (int m = 0; m < M; m++) x[m] = ld_stream<NTTMUL_NT_COLS>(tc + base_r + ((size_t)m << logs));
+  for (int m = 0; m < M; m++) x[m] = ld_stream<true>(tc + base_r + ((size_t)m << logs));
 #pragma clang loop unroll(full)
   for (int st = L1 - 1; st >= 0; st--) {
     const int dist = M >> (st + 1);
@@ -1533,8 +1279,8 @@ __global__ __launch_bounds__(256) void k_cols_inv(KParams<A> P,
   }
 #pragma clang loop unroll(full)
   for (int m = 0; m < M; m++)
-    st_stream<NTTMUL_NT_COLS>(c + base + ((size_t)m << logs),
-                              (TOut)(A::kInvCanonical ? x[m] : P.ar.canon_inv(x[m])));
+    st_stream<true>(c + base + ((size_t)m << logs),
+                    (TOut)(A::kInvCanonical ? x[m] : P.ar.canon_inv(x[m])));
 }
 
 // Column pass of the square split n = 2^8 x 2^8 (n = 65536, NTTMUL_C5_SQ): each column of 256
@@ -1574,11 +1320,9 @@ __global__ __launch_bounds__(256) void k_cols8(KParams<A> P, const TIn *__restri
   constexpr int kIS = kTile ? 4 : 8;  // log2 word stride of m on the intermediate side
   const size_t base_r = NTTMUL_HOOK_COLS_LD(DIR == 0 ? base : ibase, p, 16, ((g & 15) << 4) + cl, DIR);
   W x[16], y[16];
-  // NTTMUL_C5_BUF: one descriptor per polynomial (p is block-uniform), lane offsets relative to
-  // it (< 512 KiB), each register's constant offset as the scalar offset
-  constexpr bool kBuf = NTTMUL_C5_BUF && !NTTMUL_COLS_HOOKED && sizeof(TIn) == 8 &&
-                        sizeof(TOut) == 8 && NTTMUL_NT_COLS;
-  constexpr int kAuxB = 2;  // nt
+  // buffer instructions (see buf_ld64): one descriptor per polynomial (p is block-uniform), lane
+  // offsets relative to it (< 512 KiB), each register's constant offset as the scalar offset
+  constexpr bool kBuf = !NTTMUL_COLS_HOOKED && sizeof(TIn) == 8 && sizeof(TOut) == 8;
   const size_t pbase = p << 16;
   if constexpr (kBuf) {
     const auto ra = span_rsrc(a + pbase, 65536), rb = span_rsrc(b + pbase, 65536);
@@ -1587,28 +1331,28 @@ __global__ __launch_bounds__(256) void k_cols8(KParams<A> P, const TIn *__restri
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const int so = (Gr::off(GIN, k) << (DIR == 0 ? 8 : kIS)) * 8;
-      x[k] = (W)buf_ld64<kAuxB>(ra, lane * 8, so);
-      y[k] = NPOLY == 2 ? (W)buf_ld64<kAuxB>(rb, lane * 8, so) : W(0);
+      x[k] = (W)buf_ld64<kAuxNt>(ra, lane * 8, so);
+      y[k] = NPOLY == 2 ? (W)buf_ld64<kAuxNt>(rb, lane * 8, so) : W(0);
     }
   } else {
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const size_t o = (size_t)(Gr::base(GIN, jj) + Gr::off(GIN, k)) << (DIR == 0 ? 8 : kIS);
-      x[k] = (W)ld_stream<NTTMUL_NT_COLS>(a + base_r + o);
-      y[k] = NPOLY == 2 ? (W)ld_stream<NTTMUL_NT_COLS>(b + base_r + o) : W(0);
+      x[k] = (W)ld_stream<true>(a + base_r + o);
+      y[k] = NPOLY == 2 ? (W)ld_stream<true>(b + base_r + o) : W(0);
     }
   }
   if constexpr (DIR == 0) {
     TwPair<W> zw[16];
-    fwd_all<A, 8, 0, NPOLY, 0, 0, CW>(P.ar, x, y, lds + cl, lds + cl, P.fw, jj, 0, 0, zw);
+    fwd_all<A, 8, 0, NPOLY, 0, 0, CW>(P.ar, x, y, lds + cl, P.fw, jj, 0, 0, zw);
     if constexpr (kBuf) {
       const auto rta = span_rsrc(ta + pbase, 65536), rtb = span_rsrc(tb + pbase, 65536);
       const int lane = (int)(ibase - pbase) + (Gr::base(GOUT, jj) << kIS);
 #pragma unroll
       for (int k = 0; k < 16; k++) {
         const int so = (Gr::off(GOUT, k) << kIS) * 8;
-        buf_st64<kAuxB>(rta, lane * 8, (uint64_t)x[k], so);
-        if (NPOLY == 2) buf_st64<kAuxB>(rtb, lane * 8, (uint64_t)y[k], so);
+        buf_st64<kAuxNt>(rta, lane * 8, (uint64_t)x[k], so);
+        if (NPOLY == 2) buf_st64<kAuxNt>(rtb, lane * 8, (uint64_t)y[k], so);
       }
       return;
     }
@@ -1616,25 +1360,25 @@ __global__ __launch_bounds__(256) void k_cols8(KParams<A> P, const TIn *__restri
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const size_t o = (size_t)(Gr::base(GOUT, jj) + Gr::off(GOUT, k)) << kIS;
-      st_stream<NTTMUL_NT_COLS>(ta + base_w + o, (TOut)x[k]);
-      if (NPOLY == 2) st_stream<NTTMUL_NT_COLS>(tb + base_w + o, (TOut)y[k]);
+      st_stream<true>(ta + base_w + o, (TOut)x[k]);
+      if (NPOLY == 2) st_stream<true>(tb + base_w + o, (TOut)y[k]);
     }
   } else {
-    inv_all<A, 8, G - 1, true, 0, 0, 1, CW>(P, x, y, lds + cl, lds + cl, P.iw, jj, 0, 0);
+    inv_all<A, 8, G - 1, true, 0, 0, 1, CW>(P, x, y, lds + cl, P.iw, jj, 0, 0);
     if constexpr (kBuf) {
       const auto rc = span_rsrc(ta + pbase, 65536);
       const int lane = (int)(base - pbase) + (Gr::base(GOUT, jj) << 8);
 #pragma unroll
       for (int k = 0; k < 16; k++)
-        buf_st64<kAuxB>(rc, lane * 8, (uint64_t)(A::kInvCanonical ? x[k] : P.ar.canon_inv(x[k])),
-                        (Gr::off(GOUT, k) << 8) * 8);
+        buf_st64<kAuxNt>(rc, lane * 8, (uint64_t)(A::kInvCanonical ? x[k] : P.ar.canon_inv(x[k])),
+                         (Gr::off(GOUT, k) << 8) * 8);
       return;
     }
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const size_t o = (size_t)(Gr::base(GOUT, jj) + Gr::off(GOUT, k)) << 8;
-      st_stream<NTTMUL_NT_COLS>(ta + base + o,
-                                (TOut)(A::kInvCanonical ? x[k] : P.ar.canon_inv(x[k])));
+      st_stream<true>(ta + base + o,
+                      (TOut)(A::kInvCanonical ? x[k] : P.ar.canon_inv(x[k])));
     }
   }
 }
@@ -1719,9 +1463,9 @@ static KParams<A> product_params(const LaunchTables &T) {
   KParams<A> P = make_params<A>(T);
   static_assert(A::kBaseD == 0 || A::kBaseD == 2 || A::kBaseD == 3,
                 "planner provides F 2^D for D = 2, 3");
-  if (NTTMUL_BASE_D && A::kBaseD == 2) {
+  if (A::kBaseD == 2) {
     P.f = (W)T.f4; P.fs = (W)T.f4s; P.wf = (W)T.wf4; P.wfs = (W)T.wf4s;
-  } else if (NTTMUL_BASE_D && A::kBaseD == 3) {
+  } else if (A::kBaseD == 3) {
     P.f = (W)T.f8; P.fs = (W)T.f8s; P.wf = (W)T.wf8; P.wfs = (W)T.wf8s;
   }
   return P;

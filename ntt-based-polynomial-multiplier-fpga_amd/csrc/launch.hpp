@@ -11,7 +11,7 @@ namespace nttmul {
 // Per-device view of a plan: what a launch needs (pointers are device memory).
 struct LaunchTables {
   uint32_t logn;
-  int word_bits;           // 32 -> Arith32H / Arith32 / Arith32W by q (q < 2^32), 64 -> Arith64
+  int word_bits;           // 32 -> Arith32P / Arith32W by q (q < 2^32), 64 -> Arith64
   uint64_t q, qinv_neg;    // -q^-1 mod 2^word_bits
   uint64_t f, fs, wf, wfs; // F = n^-1 R mod q and iw[1] F, as (value, companion) pairs
   uint64_t f4, f4s, wf4, wf4s; // 4 F and iw[1] 4 F: products with incomplete transforms (D = 2)
@@ -20,7 +20,7 @@ struct LaunchTables {
   uint64_t r2;             // R^2 mod q (standalone pointwise product)
   const void *fw, *iw;     // forward / inverse twiddle (value, companion) pairs, n entries
                            // (planner.cpp tw_pair: Shoup, or Montgomery form for Arith32)
-  size_t tw_bytes = 0;     // bytes of each of fw, iw (2n pairs with Arith32's centred copies)
+  size_t tw_bytes = 0;     // bytes of each of fw, iw (n pairs)
   int cus;                 // compute units of the device (launch-shape thresholds)
   int prio = 0;            // nttmul_params.issue_prio: -1 never, 0 automatic, 1 always
   int prio_ok = 1;         // 0: the previous product launch of this context went to another

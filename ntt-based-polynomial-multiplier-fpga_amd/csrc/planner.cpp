@@ -75,7 +75,7 @@ static uint64_t companion(uint64_t w, uint64_t q, int bits) {
 
 // (value, companion) pair the device multiplies by: Shoup (w, floor(w 2^bits / q)); for
 // Arith32P (arith_select.hpp) the Plantard constant BR = B q^-1 mod 2^64, B = -w 2^64 mod q, as
-// (low, high) words; for the other 32-bit classes the Montgomery form (w 2^32 mod q, that times
+// (low, high) words; for Arith32W (q >= 2^31) the Montgomery form (w 2^32 mod q, that times
 // -q^-1 mod 2^32)
 // sgn (Arith32P only): the pair for a signed multiplicand x in [-2^31, 2^31) — the high word
 // absorbs the sign of the low one (v_mul_hi_i32 reads it as int32): c + (v >> 31)
@@ -91,24 +91,20 @@ static void tw_pair(uint64_t w, uint64_t q, int bits, uint64_t *v, uint64_t *c, 
     if (sgn) *c = (*c + (*v >> 31)) & 0xFFFFFFFFull;
     return;
   }
-  // Arith32W (q >= 2^31) always takes the Montgomery form
-  if (bits == 32 && (NTTMUL_A32_MONT || q >= (1ull << 31))) {
+  if (bits == 32) {  // Arith32W
     uint64_t inv = q;
     for (int i = 0; i < 5; i++) inv *= 2 - q * inv;
     const uint64_t w1 = (uint64_t)(((u128)w << 32) % q);
     *v = w1;
     *c = (w1 * (0 - inv)) & 0xFFFFFFFFull;
-#if NTTMUL_A32_SEILER
-    if (q < (1ull << 31)) *c = (w1 * inv) & 0xFFFFFFFFull;  // Seiler: w1 q^-1 (modarith.hpp)
-#endif
     return;
   }
   *v = w;
   *c = companion(w, q, bits);
 }
 
-// fw_logn > 0: forward table of an Arith32P plan with NTTMUL_P_TYPED 2: the entries whose
-// multiplicand is a signed in-group difference get the signed form (arith_select.hpp)
+// fw_logn > 0: forward table of an Arith32P plan: the entries whose multiplicand is a signed
+// in-group difference get the signed form (arith_select.hpp p_signed_fw_entry)
 template <class W>
 static void put_pairs(std::vector<uint8_t> &dst, const std::vector<uint64_t> &w, uint64_t q,
                       int bits, bool sgn = false, int fw_logn = 0) {
@@ -116,29 +112,11 @@ static void put_pairs(std::vector<uint8_t> &dst, const std::vector<uint64_t> &w,
   W *p = (W *)dst.data();
   for (size_t i = 0; i < w.size(); i++) {
     uint64_t v, c;
-    const bool s = sgn || (fw_logn > 0 && NTTMUL_P_TYPED >= 2 && a32_kind(q) == A32Kind::Plantard &&
+    const bool s = sgn || (fw_logn > 0 && a32_kind(q) == A32Kind::Plantard &&
                            p_signed_fw_entry(fw_logn, (uint32_t)i));
     tw_pair(w[i], q, bits, &v, &c, s);
     p[2 * i] = (W)v;
     p[2 * i + 1] = (W)c;
-  }
-}
-
-// Centred Montgomery pairs for the N-type operands of modarith.hpp's typed butterflies: after
-// the n unsigned pairs (w1 in [0, q)), the same twiddles with w1c = w1 - q when w1 > q / 2, as
-// int32 bits, and w2c = w1c (-q^-1) mod 2^32 (= w2 + 1 when shifted).
-static void append_centred(std::vector<uint8_t> &dst, uint32_t n, uint64_t q) {
-  const size_t half = dst.size();
-  dst.resize(2 * half);
-  uint32_t *p = (uint32_t *)dst.data();
-  uint64_t inv = q;
-  for (int i = 0; i < 5; i++) inv *= 2 - q * inv;
-  const uint32_t qinv_neg = (uint32_t)(0 - inv);
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t w1 = p[2 * i];
-    const uint32_t w1c = w1 > q / 2 ? (uint32_t)(w1 - q) : w1;
-    p[2 * n + 2 * i] = w1c;
-    p[2 * n + 2 * i + 1] = w1c * qinv_neg;
   }
 }
 
@@ -181,7 +159,7 @@ int make_plan(uint32_t n, uint64_t q, uint64_t psi, Plan *P, bool cyclic) {
   P->inv_psi = cyclic ? 0 : powmod(psi, q - 2, q);
   P->inv_omega = powmod(P->omega, q - 2, q);
   P->inv_n = powmod(n, q - 2, q);
-  P->word_bits = q < (1ull << 32) ? 32 : 64;  // 32: Arith32H / Arith32 / Arith32W by q
+  P->word_bits = q < (1ull << 32) ? 32 : 64;  // 32: Arith32P / Arith32W by q
   const int bits = P->word_bits;
 
   std::vector<uint64_t> fw(n, 0), iw(n, 0);
@@ -219,11 +197,7 @@ int make_plan(uint32_t n, uint64_t q, uint64_t psi, Plan *P, bool cyclic) {
   }
   if (bits == 32) {
     put_pairs<uint32_t>(P->fw, fw, q, 32, false, (int)P->logn);
-    put_pairs<uint32_t>(P->iw, iw, q, 32, NTTMUL_P_SIGNED_INV);  // GS multiplicands: differences
-    if (NTTMUL_A32_MONT && a32_kind(q) == A32Kind::Mont) {  // typed butterflies: centred copies
-      append_centred(P->fw, n, q);
-      append_centred(P->iw, n, q);
-    }
+    put_pairs<uint32_t>(P->iw, iw, q, 32, true);  // GS multiplicands: signed differences
   } else {
     put_pairs<uint64_t>(P->fw, fw, q, 64);
     put_pairs<uint64_t>(P->iw, iw, q, 64);
@@ -233,23 +207,24 @@ int make_plan(uint32_t n, uint64_t q, uint64_t psi, Plan *P, bool cyclic) {
   for (int i = 0; i < 6; i++) inv *= 2 - q * inv;
   P->qinv_neg = (0 - inv) & (bits == 32 ? 0xFFFFFFFFull : ~0ull);
   // F = n^-1 R mod q, R = 2^bits: cancels the Montgomery R^-1 of the pointwise product and the
-  // n of the unnormalised inverse transform (ntt256.C:12 scaled_inv_psi_powers' n^-1).
+  // n of the unnormalised inverse transform (ntt256.C:12 scaled_inv_psi_powers' n^-1).  The w F
+  // pairs multiply the last GS difference: signed form, like the inverse table.
   const uint64_t r_mod_q = (uint64_t)(((u128)1 << bits) % q);
   const uint64_t f = mulmod(P->inv_n, r_mod_q, q);
   tw_pair(f, q, bits, &P->f, &P->fs);
-  tw_pair(mulmod(iw[1], f, q), q, bits, &P->wf, &P->wfs, NTTMUL_P_SIGNED_INV);
+  tw_pair(mulmod(iw[1], f, q), q, bits, &P->wf, &P->wfs, true);
   const uint64_t f4 = mulmod(f, 4, q);
   tw_pair(f4, q, bits, &P->f4, &P->f4s);
-  tw_pair(mulmod(iw[1], f4, q), q, bits, &P->wf4, &P->wf4s, NTTMUL_P_SIGNED_INV);
+  tw_pair(mulmod(iw[1], f4, q), q, bits, &P->wf4, &P->wf4s, true);
   const uint64_t f8 = mulmod(f, 8, q);
   tw_pair(f8, q, bits, &P->f8, &P->f8s);
-  tw_pair(mulmod(iw[1], f8, q), q, bits, &P->wf8, &P->wf8s, NTTMUL_P_SIGNED_INV);
+  tw_pair(mulmod(iw[1], f8, q), q, bits, &P->wf8, &P->wf8s, true);
   // standalone inverse NTT: plain n^-1 (ntt256.C:12); pointwise product: R^2 mod q
   tw_pair(P->inv_n, q, bits, &P->fi, &P->fis);
-  tw_pair(mulmod(iw[1], P->inv_n, q), q, bits, &P->wfi, &P->wfis, NTTMUL_P_SIGNED_INV);
+  tw_pair(mulmod(iw[1], P->inv_n, q), q, bits, &P->wfi, &P->wfis, true);
   // the reference's unscaled inverses (intt*, inttmul*: intt(ntt(a)) = n a, ntt256.h:16-17)
   tw_pair(1, q, bits, &P->fu, &P->fus);
-  tw_pair(iw[1], q, bits, &P->wfu, &P->wfus, NTTMUL_P_SIGNED_INV);
+  tw_pair(iw[1], q, bits, &P->wfu, &P->wfus, true);
   P->r2 = mulmod(r_mod_q, r_mod_q, q);
   return NTTMUL_OK;
 }

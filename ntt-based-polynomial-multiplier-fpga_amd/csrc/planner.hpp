@@ -13,14 +13,6 @@
 
 #include "arith_select.hpp"
 
-// Arith32 twiddle form (see modarith.hpp); host tables and device kernels must agree
-#ifndef NTTMUL_A32_MONT
-#define NTTMUL_A32_MONT 1
-#endif
-#ifndef NTTMUL_A32_SEILER  // modarith.hpp: the A/B variant's tables store w1 q^-1 instead
-#define NTTMUL_A32_SEILER 0
-#endif
-
 namespace nttmul {
 
 uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q);

@@ -4,7 +4,7 @@
 //   - unsigned form: exact for every 32-bit multiplicand (the forward entries at the first stage
 //     of a register group, the column passes, the even entries elsewhere);
 //   - signed form: exact for every int32 multiplicand in (-q, q) (the odd forward entries of the
-//     in-group stages, NTTMUL_P_TYPED 2; the whole inverse table, NTTMUL_P_SIGNED_INV).
+//     in-group stages, p_signed_fw_entry; the whole inverse table).
 // The multiplication is the device sequence restated in 64-bit integer arithmetic.  Built and run
 // by tests/test_twiddle_forms.py; prints "twiddle forms ok" and exits 0 on success.
 #include <stdint.h>
@@ -52,8 +52,7 @@ int main() {
         const uint32_t *tab = (const uint32_t *)(dir ? P.iw.data() : P.fw.data());
         const std::vector<uint64_t> &ref = dir ? iw : fw;
         for (uint32_t i = 1; i < n; i++) {
-          const bool sgn = dir ? NTTMUL_P_SIGNED_INV
-                               : (NTTMUL_P_TYPED >= 2 && nttmul::p_signed_fw_entry((int)P.logn, i));
+          const bool sgn = dir || nttmul::p_signed_fw_entry((int)P.logn, i);
           signed_fw += !dir && sgn;
           const uint32_t b0 = tab[2 * i], b1 = tab[2 * i + 1], w = (uint32_t)ref[i];
           for (int t = 0; t < 24; t++) {
@@ -74,7 +73,7 @@ int main() {
     }
   }
   // the forward tables must carry signed entries (otherwise the rule silently stopped applying)
-  if (NTTMUL_P_TYPED >= 2 && signed_fw == 0) bad++;
+  if (signed_fw == 0) bad++;
   printf("%d products checked, %d signed forward entries, %d wrong\n", checked, signed_fw, bad);
   if (bad) return 1;
   printf("twiddle forms ok\n");

@@ -157,6 +157,27 @@ def test_product_sources_hold_no_kbench_code():
             assert banned not in text, (name, banned)
 
 
+def test_product_sources_hold_no_settled_switches():
+    """A compile-time switch lives in csrc/ only while a tracked tool builds both of its values
+    (DESIGN.md "Where the experiments live"): the sources hold no `#ifndef NTTMUL_<NAME>` default
+    but the kbench instrumentation points and the square-split switch that
+    test_kbench_sources_compile builds both ways.  (NTTMUL_CLOCK_STAMPS, the diagnostic library's
+    flag, is tested with #ifdef and has no default to declare.)  NTTMUL_SPLIT16 is the one settled
+    switch left: the instantiations of its dead branch change the machine code of the n = 2048
+    kernels (arith_select.hpp), so it goes in a change of its own."""
+    import re
+    allowed = re.compile(r"NTTMUL_(HOOK_[A-Z0-9_]+|C5_SQ|SPLIT16)")
+    csrc = os.path.join(nttmul.PKG_DIR, "csrc")
+    found = []
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hpp", ".hip", ".cpp")):
+            continue
+        text = open(os.path.join(csrc, name), encoding="utf-8").read()
+        found += [(name, m) for m in re.findall(r"^[ \t]*#[ \t]*ifndef[ \t]+(NTTMUL_\w+)", text, re.M)
+                  if not allowed.fullmatch(m)]
+    assert not found, found
+
+
 @pytest.mark.parametrize("flags", [
     ["-DKB_SET=1"],
     ["-DKB_SET=1", "-DKB_ABL_NOLOAD=1", "-DKB_ABL_NOSTORE=1", "-DKB_ABL_NOXCHG=1"],

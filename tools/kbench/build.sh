@@ -2,7 +2,7 @@
 # Build kbench variants: tools/kbench/build.sh [VARIANT=-Dflags ...]
 # (KB_OUT: output directory, default tools/kbench/bin; KB_FLAGS defaults to -DKB_SET=1: the n <= 4096,
 #  q < 2^31 product kernels; -DKB_SET=2: C5, 64-bit words at n = 65536.  Variants: -DKB_ABL_* pricing
-#  switches (kb_kernels.hip), or any exact A/B macro of csrc/)
+#  switches (kb_kernels.hip), or -DNTTMUL_C5_SQ=0)
 set -e
 R=$(cd "$(dirname "$0")/../.." && pwd)
 P=$R/ntt-based-polynomial-multiplier-fpga_amd

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void k_rows_w4(KParams<A> P, const uint32_t *_
                                                  const uint32_t *__restrict__ b,
                                                  uint32_t *__restrict__ c, size_t units) {
   using W = typename A::word;
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int N = Gr::N, NP = Gr::NP, G = Gr::G;
   static_assert(N / 16 == 64, "one wave per product");
   __shared__ W xch[4][NP];
@@ -191,8 +191,7 @@ __global__ __launch_bounds__(256) void k_rows_w4(KParams<A> P, const uint32_t *_
   const size_t u = (size_t)blockIdx.x * 4 + wv;
   if (u >= units) return;
   W *lx = xch[wv];
-  constexpr int kAux = NTTMUL_CPOL < 0 ? 0 : NTTMUL_CPOL;
-  constexpr int kAuxSt = NTTMUL_CPOL_ST < 0 ? 0 : NTTMUL_CPOL_ST;
+  constexpr int kAux = kAuxNt, kAuxSt = kAuxNt;
   W x[16], y[16];
   const auto ra = span_rsrc(a + u * N, N), rb = span_rsrc(b + u * N, N);
 #pragma unroll
@@ -201,11 +200,11 @@ __global__ __launch_bounds__(256) void k_rows_w4(KParams<A> P, const uint32_t *_
     x[k] = (W)buf_ld32<kAux>(ra, off);
     y[k] = (W)buf_ld32<kAux>(rb, off);
   }
-  constexpr int D = NTTMUL_BASE_D ? A::kBaseD : 0;
+  constexpr int D = A::kBaseD;
   TwPair<W> zw[16];
-  fwd_all<A, LOGS, 0, 2, D, 1>(P.ar, x, y, lx, lx, P.fw, j, 0, 0, zw);
-  base_mult<A, LOGS, D>(P.ar, x, y, zw, j);
-  inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lx, lx, P.iw, j, 0, 0);
+  fwd_all<A, LOGS, 0, 2, D, 1>(P.ar, x, y, lx, P.fw, j, 0, 0, zw);
+  base_mult<A, LOGS, D>(P.ar, x, y, zw);
+  inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lx, P.iw, j, 0, 0);
   const auto rc = span_rsrc(c + u * N, N);
 #pragma unroll
   for (int k = 0; k < 16; k++) {
@@ -229,7 +228,7 @@ __global__ __launch_bounds__(256) void k_rows_pipe(KParams<A> P, const uint32_t 
                                                    uint32_t *__restrict__ c, size_t units) {
   using W = typename A::word;
   static_assert(sizeof(W) == 4, "u32 products");
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int N = Gr::N, NP = Gr::NP, G = Gr::G;
   static_assert(N / 16 == 64, "one wave per product");
   __shared__ TwPair<W> tws[2 * N];
@@ -251,8 +250,7 @@ __global__ __launch_bounds__(256) void k_rows_pipe(KParams<A> P, const uint32_t 
   if (u >= units) return;
   W *lx = xch[wv];
   const TwPair<W> *fw = tws, *iw = tws + N;
-  constexpr int kAux = NTTMUL_CPOL < 0 ? 0 : NTTMUL_CPOL;
-  constexpr int kAuxSt = NTTMUL_CPOL_ST < 0 ? 0 : NTTMUL_CPOL_ST;
+  constexpr int kAux = kAuxNt, kAuxSt = kAuxNt;
   W x[16], y[16], nx[16], ny[16];
   {
     const auto ra = span_rsrc(a + u * N, N), rb = span_rsrc(b + u * N, N);
@@ -263,7 +261,7 @@ __global__ __launch_bounds__(256) void k_rows_pipe(KParams<A> P, const uint32_t 
       y[k] = (W)buf_ld32<kAux>(rb, off);
     }
   }
-  constexpr int D = NTTMUL_BASE_D ? A::kBaseD : 0;
+  constexpr int D = A::kBaseD;
   for (;;) {
     const size_t un = u + stride;
     const bool more = un < units;  // wave-uniform
@@ -279,9 +277,9 @@ __global__ __launch_bounds__(256) void k_rows_pipe(KParams<A> P, const uint32_t 
       __builtin_amdgcn_sched_barrier(0);
     }
     TwPair<W> zw[16];
-    fwd_all<A, LOGS, 0, 2, D, 1>(P.ar, x, y, lx, lx, fw, j, 0, 0, zw);
-    base_mult<A, LOGS, D>(P.ar, x, y, zw, j);
-    inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lx, lx, iw, j, 0, 0);
+    fwd_all<A, LOGS, 0, 2, D, 1>(P.ar, x, y, lx, fw, j, 0, 0, zw);
+    base_mult<A, LOGS, D>(P.ar, x, y, zw);
+    inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lx, iw, j, 0, 0);
     {
       const auto rc = span_rsrc(c + u * N, N);
 #pragma unroll
@@ -312,7 +310,7 @@ __global__ __launch_bounds__(128) void k_rows_ab(KParams<A> P, const uint32_t *_
                                                  uint32_t *__restrict__ c, size_t units) {
   using W = typename A::word;
   static_assert(sizeof(W) == 4, "u32 products");
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int N = Gr::N, NP = Gr::NP, G = Gr::G;
   static_assert(N / 16 == 64 && NP >= N, "one wave per polynomial");
   __shared__ W xch[2][NP];
@@ -320,17 +318,16 @@ __global__ __launch_bounds__(128) void k_rows_ab(KParams<A> P, const uint32_t *_
   const size_t u = blockIdx.x;
   if (u >= units) return;  // block-uniform
   W *lx = xch[wv];
-  constexpr int kAux = NTTMUL_CPOL < 0 ? 0 : NTTMUL_CPOL;
-  constexpr int kAuxSt = NTTMUL_CPOL_ST < 0 ? 0 : NTTMUL_CPOL_ST;
+  constexpr int kAux = kAuxNt, kAuxSt = kAuxNt;
   W x[16], y[16];
   {
     const auto r = span_rsrc((wv ? b : a) + u * N, N);
 #pragma unroll
     for (int k = 0; k < 16; k++) x[k] = (W)buf_ld32<kAux>(r, (Gr::base(0, j) + Gr::off(0, k)) * 4);
   }
-  constexpr int D = NTTMUL_BASE_D ? A::kBaseD : 0;
+  constexpr int D = A::kBaseD;
   TwPair<W> zw[16];
-  fwd_all<A, LOGS, 0, 1, D, 1>(P.ar, x, y, lx, lx, P.fw, j, 0, 0, zw);
+  fwd_all<A, LOGS, 0, 1, D, 1>(P.ar, x, y, lx, P.fw, j, 0, 0, zw);
   if (wv) {
     W *t = xch[1];
     xsync<1>();  // wave 1's last exchange reads are done before the region is overwritten
@@ -341,8 +338,8 @@ __global__ __launch_bounds__(128) void k_rows_ab(KParams<A> P, const uint32_t *_
   if (wv) return;
 #pragma unroll
   for (int k = 0; k < 16; k++) y[k] = xch[1][k * 64 + j];
-  base_mult<A, LOGS, D>(P.ar, x, y, zw, j);
-  inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lx, lx, P.iw, j, 0, 0);
+  base_mult<A, LOGS, D>(P.ar, x, y, zw);
+  inv_all<A, LOGS, G - 1, true, D, 1>(P, x, y, lx, P.iw, j, 0, 0);
   const auto rc = span_rsrc(c + u * N, N);
 #pragma unroll
   for (int k = 0; k < 16; k++) {
@@ -453,7 +450,7 @@ __global__ __launch_bounds__(256) void k_mp_persist(KParams<A> P, const IO *__re
                                                     unsigned batch, MpSync S) {
   using W = typename A::word;
   constexpr int LOGS = 12, NR = 1 << L1, M = 1 << L1;
-  using Gr = Groups<LOGS, kWT<A, LOGS>()>;
+  using Gr = Groups<LOGS>;
   constexpr int N = Gr::N, G = Gr::G, NP = Gr::NP;
   constexpr unsigned T = 2 * kMpCols + NR;
   constexpr size_t kPoly = (size_t)N << L1;   // words per polynomial
@@ -517,11 +514,11 @@ __global__ __launch_bounds__(256) void k_mp_persist(KParams<A> P, const IO *__re
           x[q] = ld_pol<NTTMUL_MP_POL>(ta + base + Gr::off(0, q));
           y[q] = ld_pol<NTTMUL_MP_POL>(tb + base + Gr::off(0, q));
         }
-        constexpr int D = NTTMUL_BASE_D ? A::kBaseD : 0;
+        constexpr int D = A::kBaseD;
         TwPair<W> zw[16];
-        fwd_all<A, LOGS, 0, 2, D>(P.ar, x, y, lds, lds, P.fw, j, row, L1, zw);
-        base_mult<A, LOGS, D>(P.ar, x, y, zw, j);
-        inv_all<A, LOGS, G - 1, false, D>(P, x, y, lds, lds, P.iw, j, row, L1);
+        fwd_all<A, LOGS, 0, 2, D>(P.ar, x, y, lds, P.fw, j, row, L1, zw);
+        base_mult<A, LOGS, D>(P.ar, x, y, zw);
+        inv_all<A, LOGS, G - 1, false, D>(P, x, y, lds, P.iw, j, row, L1);
 #pragma unroll
         for (int q = 0; q < 16; q++) st_pol<NTTMUL_MP_POL>(tc + base + Gr::off(0, q), x[q]);
         mp_publish(S.cnt + batch + p);
@@ -536,8 +533,8 @@ __global__ __launch_bounds__(256) void k_mp_persist(KParams<A> P, const IO *__re
         W x[M], y[M];
 #pragma clang loop unroll(full)
         for (int m = 0; m < M; m++) {
-          x[m] = (W)ld_pol<NTTMUL_NT_COLS>(a + base + ((size_t)m << LOGS));
-          y[m] = (W)ld_pol<NTTMUL_NT_COLS>(b + base + ((size_t)m << LOGS));
+          x[m] = (W)ld_pol<1>(a + base + ((size_t)m << LOGS));
+          y[m] = (W)ld_pol<1>(b + base + ((size_t)m << LOGS));
         }
 #pragma clang loop unroll(full)
         for (int st = 0; st < L1; st++) {
@@ -753,15 +750,11 @@ static hipError_t launch_(const LaunchTables &T, const Conf &C, const void *a, c
 #else  // u32 words, q < 2^31, n <= 4096
   if (T.word_bits != 32 || T.q >= (1ull << 31) || T.logn > 12 || io_bits != 32)
     return hipErrorNotSupported;
-  switch (a32_kind(T.q)) {
-    case A32Kind::Harvey: return fused<Arith32H>(T, C, a, b, c, batch, s);
-    case A32Kind::Plantard:
-      if (T.logn == 12 && p3_fold_ok(T.q))
-        return launch_rows<Arith32P3, uint32_t, uint32_t, 12, 0>(product_params<Arith32P3>(T), a,
-                                                                 b, c, batch, s);
-      return fused<Arith32P>(T, C, a, b, c, batch, s);
-    default: return fused<Arith32>(T, C, a, b, c, batch, s);
-  }
+  // (q < 2^31: a32_kind is Plantard)
+  if (T.logn == 12 && p3_fold_ok(T.q))
+    return launch_rows<Arith32P3, uint32_t, uint32_t, 12, 0>(product_params<Arith32P3>(T), a, b, c,
+                                                             batch, s);
+  return fused<Arith32P>(T, C, a, b, c, batch, s);
 #endif
 }
 
