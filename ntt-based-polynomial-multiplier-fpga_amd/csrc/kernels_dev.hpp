@@ -96,16 +96,9 @@ struct KParams {
   typename A::word wf, wfs;            // iw[1] * F mod q
 };
 
-// Dry run of the product dispatch (describe_polymul -> nttmul_kernel_name): while tl_describe is
-// set, the launchers append the kernels they would launch to it and launch nothing, so the name
-// the bench reports comes from the same dispatch code that runs.
-static thread_local std::string *tl_describe = nullptr;
+// Kernel names as the dry run of the product dispatch spells them (emit, at the end of this file)
 template <class A> struct AName;
 template <class T> constexpr const char *word_name() { return sizeof(T) == 8 ? "u64" : "u32"; }
-static void describe_add(const std::string &k) {
-  if (!tl_describe->empty()) *tl_describe += " + ";
-  *tl_describe += k;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Layout algebra of the register groups (all compile-time except the per-thread base)
@@ -1485,41 +1478,82 @@ static KParams<A> product_params(const LaunchTables &T) {
 // next block overlap the others' arithmetic).  So: on when the launch has at most 4 waves per
 // SIMD of the device and the previous product launch of the context went to the same stream
 // (T.prio_ok, nttmul.cpp run_device: launches alternating over two streams overlap, and then the
-// oldest-first order wins, 292 vs 262 M/s at C2); nttmul_params.issue_prio -1 / 1 forces it off /
-// on for a context.
-static thread_local int tl_prio_cus = 0;   // launch_polymul: T.cus, or 0 when T.prio_ok is 0
-static thread_local int tl_prio_mode = 0;  // launch_polymul: T.prio (nttmul_params.issue_prio)
-static bool rows_prio(size_t waves) {
-  if (tl_prio_mode) return tl_prio_mode > 0;
-  return waves <= (size_t)tl_prio_cus * 4 * 4;  // 4 SIMDs per CU, 4 waves per SIMD
+// oldest-first order wins, 292 vs 262 M/s at C2); nttmul_params.issue_prio -1 / 1 (T.prio) forces
+// it off / on for a context.  The rule reads everything from the launch's own LaunchTables.
+static bool rows_prio(const LaunchTables &T, size_t waves) {
+  if (T.prio) return T.prio > 0;
+  return waves <= (size_t)(T.prio_ok ? T.cus : 0) * 4 * 4;  // 4 SIMDs per CU, 4 waves per SIMD
 }
 
-template <class A, class TIn, class TOut, int LOGS, int L1>
-static hipError_t launch_rows(const KParams<A> &P, const void *a, const void *b, void *c,
-                              size_t units, hipStream_t s) {
-  constexpr int NT = rows_threads(LOGS), PB = NT / ((1 << LOGS) / 16);
-  const size_t blocks = (units + PB - 1) / PB;
-  // (the prioritised variant exists for the u32 Plantard products only: q < 2^31, C2 / C3 family)
-  constexpr bool kPrioOk = L1 == 0 && IsPlantard<A>::value && sizeof(TIn) == 4 && sizeof(TOut) == 4;
-  const bool prio = kPrioOk && blocks && rows_prio(blocks * (NT / 64));
-  if (tl_describe) {
-    describe_add(std::string("k_rows<") + AName<A>::v + "," + word_name<TIn>() + "," +
-                 word_name<TOut>() + "," + std::to_string(LOGS) + "," + std::to_string(L1) +
-                 (prio ? ",prio>" : ">"));
-    return hipSuccess;
-  }
+// Where a product launcher sends its kernels: onto stream s, or, in the dry run behind
+// nttmul_kernel_name (describe_polymul), as names into *describe.  The launchers hold no launch of
+// their own: every kernel of a product goes through emit, whose describing branch returns before
+// the launch, so the names come from the very statements that launch and a dry run (null operand
+// pointers) cannot start a kernel.
+struct Emit {
+  hipStream_t s;
+  std::string *describe;
+};
+template <class T> struct NoDeduce { using type = T; };
+
+// `blocks` workgroups of `threads` of `kernel` on stream s (nothing for an empty grid); the
+// arguments convert to the kernel's parameter types as in a direct call
+template <class... KArgs>
+static hipError_t launch(void (*kernel)(KArgs...), size_t blocks, int threads, hipStream_t s,
+                         typename NoDeduce<KArgs>::type... args) {
   if (blocks == 0) return hipSuccess;
-  if constexpr (kPrioOk) {
-    if (prio) {
-      hipLaunchKernelGGL((k_rows<A, TIn, TOut, LOGS, L1, true>), dim3((unsigned)blocks), dim3(NT), 0,
-                         s, P, (const TIn *)a, (const TIn *)b, (TOut *)c, units);
-      return hipGetLastError();
-    }
-  }
-  hipLaunchKernelGGL((k_rows<A, TIn, TOut, LOGS, L1>), dim3((unsigned)blocks), dim3(NT), 0, s, P,
-                     (const TIn *)a, (const TIn *)b, (TOut *)c, units);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), 0, s, args...);
   return hipGetLastError();
 }
 
+// name() is only called in the dry run, so a launch builds no string
+template <class Name, class... KArgs>
+static hipError_t emit(const Emit &E, Name name, void (*kernel)(KArgs...), size_t blocks,
+                       int threads, typename NoDeduce<KArgs>::type... args) {
+  if (E.describe) {
+    if (!E.describe->empty()) *E.describe += " + ";
+    *E.describe += name();
+    return hipSuccess;
+  }
+  return launch(kernel, blocks, threads, E.s, args...);
+}
+
+// f(std::integral_constant<int, LOGS>) for the row sizes one launch covers, n = 2^8 .. 2^12
+template <class F>
+static hipError_t with_logn(uint32_t logn, F f) {
+  switch (logn) {
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 9: return f(std::integral_constant<int, 9>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 11: return f(std::integral_constant<int, 11>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The row pass of a product: `units` rows of 2^LOGS coefficients after L1 column stages (L1 = 0:
+// the fused product of whole polynomials)
+template <class A, class TIn, class TOut, int LOGS, int L1>
+static hipError_t launch_rows(const LaunchTables &T, const void *a, const void *b, void *c,
+                              size_t units, const Emit &E) {
+  constexpr int NT = rows_threads(LOGS), PB = NT / ((1 << LOGS) / 16);
+  const size_t blocks = (units + PB - 1) / PB;
+  const KParams<A> P = product_params<A>(T);
+  // (the prioritised variant exists for the u32 Plantard products only: q < 2^31, C2 / C3 family)
+  constexpr bool kPrioOk = L1 == 0 && IsPlantard<A>::value && sizeof(TIn) == 4 && sizeof(TOut) == 4;
+  const bool prio = kPrioOk && blocks && rows_prio(T, blocks * (NT / 64));
+  const char *end = prio ? ",prio>" : ">";
+  const auto name = [end] {
+    return std::string("k_rows<") + AName<A>::v + "," + word_name<TIn>() + "," +
+           word_name<TOut>() + "," + std::to_string(LOGS) + "," + std::to_string(L1) + end;
+  };
+  if constexpr (kPrioOk) {
+    if (prio)
+      return emit(E, name, k_rows<A, TIn, TOut, LOGS, L1, true>, blocks, NT, P, (const TIn *)a,
+                  (const TIn *)b, (TOut *)c, units);
+  }
+  return emit(E, name, k_rows<A, TIn, TOut, LOGS, L1>, blocks, NT, P, (const TIn *)a,
+              (const TIn *)b, (TOut *)c, units);
+}
 
 }  // namespace nttmul

@@ -22,9 +22,11 @@ struct LaunchTables {
                            // (planner.cpp tw_pair: Shoup, or Montgomery form for Arith32)
   size_t tw_bytes = 0;     // bytes of each of fw, iw (n pairs)
   int cus;                 // compute units of the device (launch-shape thresholds)
+  // The issue-priority rule (kernels_dev.hpp rows_prio) reads these three from the tables of the
+  // launch itself: no state outlives a call
   int prio = 0;            // nttmul_params.issue_prio: -1 never, 0 automatic, 1 always
   int prio_ok = 1;         // 0: the previous product launch of this context went to another
-                           // stream, so automatic mode keeps oldest-first issue (kernels.hip rows_prio)
+                           // stream, so automatic mode keeps oldest-first issue
 };
 
 // c = a * b for `batch` polynomials of n = 2^logn words of io_bits (32/64) each, on stream s.
@@ -32,7 +34,9 @@ struct LaunchTables {
 hipError_t launch_polymul(const LaunchTables &T, const void *a, const void *b, void *c,
                           size_t batch, int io_bits, void **scr, hipStream_t s);
 // The kernels launch_polymul would launch for (T, io_bits), as "k_rows<Arith32P3,u32,u32,12,0>"
-// (multi-pass: the three kernels joined by " + "); nothing is launched.
+// (multi-pass: the three kernels joined by " + ").  It runs the dispatch of launch_polymul itself
+// with a describing Emit (kernels_dev.hpp): each kernel's name is appended by the statement that
+// would launch it, and that statement returns before the launch.
 hipError_t describe_polymul(const LaunchTables &T, int io_bits, size_t batch, std::string *out);
 // Standalone forward (inverse = 0) or inverse (inverse = 1) NTT of `batch` polynomials
 // (SURVEY §8f row 1).  scr as for launch_polymul (only scr[0] is used).

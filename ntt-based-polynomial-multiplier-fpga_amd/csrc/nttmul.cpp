@@ -182,6 +182,28 @@ LaunchTables tables_for(const nttmul_ctx *ctx, const DevState &d) {
   return T;
 }
 
+// Words of io_bits exist (32 or 64) and hold every residue mod q
+bool io_ok(const nttmul_ctx *ctx, int io_bits) {
+  return io_bits == 64 || (io_bits == 32 && ctx->plan.q <= 0xFFFFFFFFull);
+}
+
+// A chunk of `bytes` per operand runs zero-copy (params.zero_copy_kb): the kernel reads a, b from
+// and writes c to the pinned staging buffers over PCIe, with no copy-engine round trips (small
+// transactions, the ntt256_product* shims).  Single-launch sizes only.
+bool zero_copy_chunk(const nttmul_ctx *ctx, size_t bytes) {
+  return bytes <= ctx->zero_copy && ctx->plan.logn <= 12;
+}
+
+// name into (buf, cap), truncated and terminated; the untruncated length
+int copy_name(char *buf, size_t cap, const std::string &name) {
+  if (cap) {
+    const size_t k = std::min(cap - 1, name.size());
+    memcpy(buf, name.data(), k);
+    buf[k] = 0;
+  }
+  return (int)name.size();
+}
+
 DevState *find_dev(nttmul_ctx *ctx, int dev) {
   for (int i = 0; i < ctx->ndev; i++)
     if (ctx->dev[i].id == dev) return &ctx->dev[i];
@@ -257,8 +279,7 @@ void note_product(nttmul_ctx *ctx, const DevState &d, size_t batch, int io_bits,
 int run_device(nttmul_ctx *ctx, DevState &d, Scratch &sc, int op, void *c, const void *a,
                const void *b, size_t batch, int io_bits, hipStream_t s) {
   const Plan &P = ctx->plan;
-  if (io_bits != 32 && io_bits != 64) return NTTMUL_EINVAL;
-  if (io_bits == 32 && P.q > 0xFFFFFFFFull) return NTTMUL_EINVAL;  // q does not fit the words
+  if (!io_ok(ctx, io_bits)) return NTTMUL_EINVAL;
   if (!batch) return NTTMUL_OK;  // an empty batch: nothing enqueued, no pointer dereferenced
   if (ctx->flags & NTTMUL_FLAG_VALIDATE) {
     HIP_TRY(ctx, hipMemsetAsync(d.flag, 0, sizeof(int), s));
@@ -390,7 +411,7 @@ struct HostJob {
   int op, io_bits;
   void *c;
   const void *a, *b;
-  size_t pbytes, chunk, zero_copy;
+  size_t pbytes, chunk;
   bool direct;
 };
 
@@ -416,45 +437,32 @@ int run_host_dev(nttmul_ctx *ctx, DevState &d, const HostJob &J, size_t p0, size
     const int s = (int)(k++ % kSlots);
     const size_t cnt = std::min(J.chunk, p1 - next);
     const size_t off = next * J.pbytes, bytes = cnt * J.pbytes;
+    // the chunk's host side: the caller's own buffers (direct), or the slot's pinned staging,
+    // filled here once the slot's previous chunk has left it
+    const void *ha = (const char *)J.a + off, *hb = two ? (const char *)J.b + off : nullptr;
+    void *hc = (char *)J.c + off;
+    if (!J.direct) {
+      if ((st = retire(s))) break;
+      pcopy(ctx, d.pin[s][0], ha, bytes);
+      if (two) pcopy(ctx, d.pin[s][1], hb, bytes);
+      ha = d.pin[s][0], hb = d.pin[s][1], hc = d.pin[s][2];
+    }
+    // its device side: the slot's device buffers between two copies, or the staging itself
+    const bool zero_copy = !J.direct && zero_copy_chunk(ctx, bytes);
+    void *const *dv = zero_copy ? d.pin_dev[s] : d.dbuf[s];
     hipError_t e = hipSuccess;
-    if (J.direct) {
-      e = hipMemcpyAsync(d.dbuf[s][0], (const char *)J.a + off, bytes, hipMemcpyHostToDevice,
-                         d.xs[s]);
+    if (!zero_copy) {
+      e = hipMemcpyAsync(dv[0], ha, bytes, hipMemcpyHostToDevice, d.xs[s]);
       if (e == hipSuccess && two)
-        e = hipMemcpyAsync(d.dbuf[s][1], (const char *)J.b + off, bytes, hipMemcpyHostToDevice,
-                           d.xs[s]);
+        e = hipMemcpyAsync(dv[1], hb, bytes, hipMemcpyHostToDevice, d.xs[s]);
       if (e != hipSuccess) { st = fail(ctx, e, "hipMemcpyAsync H2D"); break; }
-      if ((st = run_device(ctx, d, d.sscr[s], J.op, d.dbuf[s][2], d.dbuf[s][0], d.dbuf[s][1],
-                           cnt, J.io_bits, d.xs[s])))
-        break;
-      e = hipMemcpyAsync((char *)J.c + off, d.dbuf[s][2], bytes, hipMemcpyDeviceToHost, d.xs[s]);
-      if (e != hipSuccess) { st = fail(ctx, e, "hipMemcpyAsync D2H"); break; }
-      slot[s] = Pending{true, off, bytes};
-      next += cnt;
-      continue;
     }
-    if ((st = retire(s))) break;
-    pcopy(ctx, d.pin[s][0], (const char *)J.a + off, bytes);
-    if (two) pcopy(ctx, d.pin[s][1], (const char *)J.b + off, bytes);
-    if (bytes <= J.zero_copy && ctx->plan.logn <= 12) {
-      // small transaction (the ntt256_product* shims): the kernel reads a, b from and writes c to
-      // the pinned staging buffers over PCIe — no copy-engine round trips
-      if ((st = run_device(ctx, d, d.sscr[s], J.op, d.pin_dev[s][2], d.pin_dev[s][0],
-                           d.pin_dev[s][1], cnt, J.io_bits, d.xs[s])))
-        break;
-      slot[s] = Pending{true, off, bytes};
-      next += cnt;
-      continue;
-    }
-    e = hipMemcpyAsync(d.dbuf[s][0], d.pin[s][0], bytes, hipMemcpyHostToDevice, d.xs[s]);
-    if (e == hipSuccess && two)
-      e = hipMemcpyAsync(d.dbuf[s][1], d.pin[s][1], bytes, hipMemcpyHostToDevice, d.xs[s]);
-    if (e != hipSuccess) { st = fail(ctx, e, "hipMemcpyAsync H2D"); break; }
-    if ((st = run_device(ctx, d, d.sscr[s], J.op, d.dbuf[s][2], d.dbuf[s][0], d.dbuf[s][1], cnt,
-                         J.io_bits, d.xs[s])))
+    if ((st = run_device(ctx, d, d.sscr[s], J.op, dv[2], dv[0], dv[1], cnt, J.io_bits, d.xs[s])))
       break;
-    e = hipMemcpyAsync(d.pin[s][2], d.dbuf[s][2], bytes, hipMemcpyDeviceToHost, d.xs[s]);
-    if (e != hipSuccess) { st = fail(ctx, e, "hipMemcpyAsync D2H"); break; }
+    if (!zero_copy) {
+      e = hipMemcpyAsync(hc, dv[2], bytes, hipMemcpyDeviceToHost, d.xs[s]);
+      if (e != hipSuccess) { st = fail(ctx, e, "hipMemcpyAsync D2H"); break; }
+    }
     slot[s] = Pending{true, off, bytes};
     next += cnt;
   }
@@ -683,9 +691,7 @@ int run_host(nttmul_ctx *ctx, int op, void *c, const void *a, const void *b, siz
              int io_bits) {
   const bool two = op == OP_MULTIPLY || op == OP_POINTWISE;
   // pointers may be null for an empty batch, as on the device path (device_op)
-  if (!ctx || (batch && (!c || !a || (two && !b)))) return NTTMUL_EINVAL;
-  if (io_bits != 32 && io_bits != 64) return NTTMUL_EINVAL;
-  if (io_bits == 32 && ctx->plan.q > 0xFFFFFFFFull) return NTTMUL_EINVAL;
+  if (!ctx || (batch && (!c || !a || (two && !b))) || !io_ok(ctx, io_bits)) return NTTMUL_EINVAL;
   if (!batch) return NTTMUL_OK;
   if (op == OP_MULTIPLY && io_bits == 32) {  // (no HIP call on the server's fast path)
     const int st = run_server(ctx, c, a, b, batch);
@@ -701,14 +707,10 @@ int run_host(nttmul_ctx *ctx, int op, void *c, const void *a, const void *b, siz
   J.b = b;
   J.pbytes = (size_t)ctx->plan.n * (io_bits / 8);
   J.chunk = std::max<size_t>(1, kChunkBytes / J.pbytes);
-  // per-operand bytes up to which a chunk runs zero-copy on the pinned staging buffers
-  // (params.zero_copy_kb)
-  J.zero_copy = ctx->zero_copy;
   const size_t total = batch * J.pbytes;
   J.direct = host_pinned(a, total) && (!two || host_pinned(b, total)) && host_pinned(c, total);
   const size_t first_chunk = std::min(J.chunk, std::max<size_t>(1, batch / ctx->ndev));
-  ctx->last_path = J.direct ? 1 : (first_chunk * J.pbytes <= J.zero_copy &&
-                                   ctx->plan.logn <= 12) ? 2 : 0;
+  ctx->last_path = J.direct ? 1 : zero_copy_chunk(ctx, first_chunk * J.pbytes) ? 2 : 0;
   int status[kMaxDev] = {};
   std::vector<std::thread> th;
   for (int i = 1; i < ctx->ndev; i++) {
@@ -919,17 +921,11 @@ int nttmul_server_status(const nttmul_ctx *ctx, char *reason, size_t cap) {
 
 int nttmul_kernel_name_batch(const nttmul_ctx *ctx, int word_bits, size_t batch, char *buf,
                              size_t cap) {
-  if (!ctx || (word_bits != 32 && word_bits != 64) || (cap && !buf)) return NTTMUL_EINVAL;
-  if (word_bits == 32 && ctx->plan.q > 0xFFFFFFFFull) return NTTMUL_EINVAL;
+  if (!ctx || !io_ok(ctx, word_bits) || (cap && !buf)) return NTTMUL_EINVAL;
   std::string name;
   if (describe_polymul(tables_for(ctx, ctx->dev[0]), word_bits, batch, &name) != hipSuccess)
     return NTTMUL_EUNSUPPORTED;
-  if (cap) {
-    const size_t k = std::min(cap - 1, name.size());
-    memcpy(buf, name.data(), k);
-    buf[k] = 0;
-  }
-  return (int)name.size();
+  return copy_name(buf, cap, name);
 }
 int nttmul_kernel_name(const nttmul_ctx *ctx, int word_bits, char *buf, size_t cap) {
   return nttmul_kernel_name_batch(ctx, word_bits, 0, buf, cap);
@@ -952,12 +948,7 @@ int nttmul_last_kernel_name(const nttmul_ctx *ctx, char *buf, size_t cap) {
     T.prio_ok = prio_ok;
     if (describe_polymul(T, io_bits, batch, &name) != hipSuccess) return NTTMUL_EUNSUPPORTED;
   }
-  if (cap) {
-    const size_t k = std::min(cap - 1, name.size());
-    memcpy(buf, name.data(), k);
-    buf[k] = 0;
-  }
-  return (int)name.size();
+  return copy_name(buf, cap, name);
 }
 
 int nttmul_multiply_batch_u32(nttmul_ctx *ctx, uint32_t *c, const uint32_t *a, const uint32_t *b,
@@ -1041,8 +1032,7 @@ int nttmul_pointwise_batch_device(nttmul_ctx *ctx, void *c, const void *a, const
 
 int nttmul_fill_random_device(nttmul_ctx *ctx, void *a, void *b, uint64_t p0, size_t count,
                               uint64_t seed, int word_bits, int dev, void *stream) {
-  if (!ctx || (count && (!a || !b)) || (word_bits != 32 && word_bits != 64)) return NTTMUL_EINVAL;
-  if (word_bits == 32 && ctx->plan.q > 0xFFFFFFFFull) return NTTMUL_EINVAL;
+  if (!ctx || (count && (!a || !b)) || !io_ok(ctx, word_bits)) return NTTMUL_EINVAL;
   DevState *d = find_dev(ctx, dev);
   if (!d) return NTTMUL_ENODEV;
   if (const int st = server_quiesce(ctx)) return st;

@@ -348,6 +348,20 @@ def test_zero_copy_knob(zc, path, torch_cuda):
     assert np.array_equal(got[0], O.Plan(n, q).product_merged(a[0], b[0]))
 
 
+def test_zero_copy_slot_reuse(torch_cuda):
+    """Zero-copy chunks over reused slots (nttmul.cpp run_host_dev): with zero_copy_kb at the
+    8 MiB chunk size, a pageable u32 call of 3 * 2048 + 5 products of n = 1024 is four chunks
+    (the last one partial) over three slots, so slot 0's first result must leave its staging
+    buffer before the fourth chunk's operands are copied in.  Every product is the oracle's."""
+    n, q, batch = 1024, Q31, 3 * 2048 + 5
+    ctx = _ctx(n, q, zero_copy_kb=8192, small_server=-1)
+    a, b = O.fill_inputs(n, q, 29, batch)
+    c = ctx.multiply(a.astype(np.uint32), b.astype(np.uint32)).astype(np.uint64)
+    assert ctx.last_host_path() == 2
+    ref = O.Plan(n, q).product_batch(a, b)[0]
+    assert np.array_equal(c, ref.reshape(batch, n))
+
+
 def test_issue_priority_follows_streams(torch_cuda):
     """Calls alternating over two streams overlap, so the library leaves the issue priority off
     for them (nttmul.cpp run_device); consecutive calls on one stream get it.  The last launch is

@@ -609,7 +609,7 @@ static hipError_t fused(const LaunchTables &T, const Conf &C, const void *a, con
       constexpr int NT = rows_threads(10), PB = NT / 64;
       const size_t blocks = (batch + PB - 1) / PB;
       if (blocks == 0) return hipSuccess;
-      const bool prio = rows_prio(blocks * (NT / 64));
+      const bool prio = rows_prio(T, blocks * (NT / 64));
       if (prio)
         hipLaunchKernelGGL((k_rows_pl<A, uint32_t, uint32_t, 10, 0, true>), dim3((unsigned)blocks),
                            dim3(NT), 0, s, (const uint32_t *)a, (const uint32_t *)b,
@@ -622,14 +622,10 @@ static hipError_t fused(const LaunchTables &T, const Conf &C, const void *a, con
     }
   }
 #endif
-  switch (T.logn) {
-    case 8: return launch_rows<A, uint32_t, uint32_t, 8, 0>(P, a, b, c, batch, s);
-    case 9: return launch_rows<A, uint32_t, uint32_t, 9, 0>(P, a, b, c, batch, s);
-    case 10: return launch_rows<A, uint32_t, uint32_t, 10, 0>(P, a, b, c, batch, s);
-    case 11: return launch_rows<A, uint32_t, uint32_t, 11, 0>(P, a, b, c, batch, s);
-    case 12: return launch_rows<A, uint32_t, uint32_t, 12, 0>(P, a, b, c, batch, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_logn(T.logn, [&](auto logs) {
+    return launch_rows<A, uint32_t, uint32_t, decltype(logs)::value, 0>(T, a, b, c, batch,
+                                                                        Emit{s, nullptr});
+  });
 }
 
 // The library's three-launch multi-pass product (kernels.hip multipass_l1), one pass at a time
@@ -724,22 +720,10 @@ static hipError_t multipass_persist(const LaunchTables &T, const Conf &C, const 
   return hipGetLastError();
 }
 
-static hipError_t launch_(const LaunchTables &T, const Conf &C, const void *a, const void *b,
-                          void *c, size_t batch, int io_bits, void **scr, hipStream_t s);
-// the library's launch_polymul rule for the issue-priority variant (kernels_dev.hpp rows_prio):
-// one-generation launches of the Plantard kernels take it (C2), unless T.prio says otherwise
+// (the issue-priority variant follows the library's rule, kernels_dev.hpp rows_prio on T:
+// one-generation launches of the Plantard kernels take it (C2), unless T.prio says otherwise)
 hipError_t launch(const LaunchTables &T, const Conf &C, const void *a, const void *b, void *c,
                   size_t batch, int io_bits, void **scr, hipStream_t s) {
-  const int prev = tl_prio_cus, prev_mode = tl_prio_mode;
-  tl_prio_cus = T.prio_ok ? T.cus : 0;
-  tl_prio_mode = T.prio;
-  const hipError_t e = launch_(T, C, a, b, c, batch, io_bits, scr, s);
-  tl_prio_cus = prev;
-  tl_prio_mode = prev_mode;
-  return e;
-}
-static hipError_t launch_(const LaunchTables &T, const Conf &C, const void *a, const void *b,
-                          void *c, size_t batch, int io_bits, void **scr, hipStream_t s) {
 #if KB_SET == 2  // C5: 64-bit words, n = 65536
   if (T.word_bits != 64 || T.logn != 16 || io_bits != 64) return hipErrorNotSupported;
   if (C.mp_lag > 0 && scr[3])
@@ -752,8 +736,7 @@ static hipError_t launch_(const LaunchTables &T, const Conf &C, const void *a, c
     return hipErrorNotSupported;
   // (q < 2^31: a32_kind is Plantard)
   if (T.logn == 12 && p3_fold_ok(T.q))
-    return launch_rows<Arith32P3, uint32_t, uint32_t, 12, 0>(product_params<Arith32P3>(T), a, b, c,
-                                                             batch, s);
+    return launch_rows<Arith32P3, uint32_t, uint32_t, 12, 0>(T, a, b, c, batch, Emit{s, nullptr});
   return fused<Arith32P>(T, C, a, b, c, batch, s);
 #endif
 }
