@@ -1,0 +1,312 @@
+"""Case tables of the GPU suite and a pure-Python mirror of the library's kernel selection.
+
+Two things live here, both plain data and arithmetic (no GPU, no library, no oracle):
+
+* the axes the GPU tests are parametrised over (moduli, sizes, word widths, batches, modes), as
+  `Case` rows, so that what the suite launches is written down in one place;
+* `kernels_of(case)`: the kernels a case launches, as `nttmul.kernel_key` strings, restating the
+  selection rules of csrc/kernels.hip (with_arith, with_io, product, xform, launch_pointwise,
+  launch_bitrev, launch_fill, launch_check_range, launch_server), csrc/kernels_dev.hpp
+  (launch_rows, rows_prio, xform_upg) and csrc/nttmul.cpp (run_device, run_server).
+
+tests/test_kernel_ledger.py holds the two against the built library: every kernel of
+libnttmul.so is either launched by a case or matched by an `UNREACHABLE` rule with its reason,
+and every kernel a case names exists.  tests/test_gpu_ledger.py anchors the product part of the
+mirror to the library's own dispatch (nttmul_kernel_name).
+"""
+from collections import namedtuple
+
+Q0 = 12289
+Q20 = 786433                # 3 * 2^18 + 1, 20 bits
+Q31 = 2013265921            # 15 * 2^27 + 1, the benchmark modulus
+Q30 = 1073479681            # < 2^30
+Q32 = 4293918721            # 0xFFF00001, full 32-bit word
+Q62 = 0x3FFFFFFFFFE80001    # 62-bit, 2^17 | q - 1
+Q31HI = 2147352577          # the ends of the Arith32P3 range 2^30 < q < 2^31, 2^17 | q - 1
+Q31LO = 1073872897
+SEED33 = 33
+Q33 = 7863402497            # test_gpu_parity._random_primes([33], 17, SEED33)[0]
+
+PLANTARD = (Q31HI, Q31LO, Q31, Q20)     # Arith32P
+WIDE = (Q32,)                           # Arith32W
+ARITH64 = (Q62, Q33)                    # Arith64
+# one modulus per arithmetic class
+CLASS_MODULI = (Q31HI, Q32, Q62)
+
+XF_MODES = (0, 2, 1, 3, 1 | 4, 3 | 4)   # nttmul.XF_INVERSE = 1, XF_REV2STD = 2, XF_UNSCALED = 4
+ALL_N = (256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536)
+MULTIPASS_N = (8192, 16384, 32768, 65536)
+MI355X_CUS = 256
+
+# op: "multiply" | "transform" | "pointwise" | "fill"
+# path: "device" (the *_device entry points and the launch path of the host calls) or "server"
+#   (a host multiply the resident server takes: run_server's eligibility holds)
+# mode: transform mode bits;  validate: NTTMUL_FLAG_VALIDATE;  prio: nttmul_params.issue_prio;
+# prio_ok: LaunchTables.prio_ok (0 after a product launch on another stream)
+Case = namedtuple("Case", "op n q word_bits batch mode validate path prio prio_ok",
+                  defaults=(0, False, "device", 0, 1))
+
+
+def native_bits(q):
+    return 32 if q < (1 << 32) else 64
+
+
+def word_options(q):
+    """The word widths a caller may pass for q: the native one, and 64 on a 32-bit modulus."""
+    return (32, 64) if q < (1 << 32) else (64,)
+
+
+# ---------------------------------------------------------------------------------------------
+# The mirror
+# ---------------------------------------------------------------------------------------------
+
+def arith_class(q):
+    """kernels.hip with_arith on planner.cpp's word_bits: the class follows q alone."""
+    return "Arith32P" if q < (1 << 31) else "Arith32W" if q < (1 << 32) else "Arith64"
+
+
+def p3_fold_ok(q):
+    """arith_select.hpp p3_fold_ok."""
+    if q >= (1 << 31) or q < 3:
+        return False
+    s1 = 4 * (q - 1) * (q - 1)
+    return (s1 >> 32) * ((1 << 32) % q) + 0xFFFFFFFF + s1 < (1 << 64)
+
+
+def _io(bits):
+    return "u32" if bits == 32 else "u64"
+
+
+def _logn(n):
+    assert n & (n - 1) == 0 and 256 <= n <= 65536
+    return n.bit_length() - 1
+
+
+def square_split(n, q):
+    """64-bit arithmetic at n = 65536 runs 256 x 256 (NTTMUL_C5_SQ)."""
+    return n == 65536 and q >= (1 << 32)
+
+
+def row_split(n, q):
+    """(LOGS, L1): the row pass a product or transform of n words runs, after L1 column stages."""
+    logn = _logn(n)
+    if logn <= 12:
+        return logn, 0
+    return (8, 8) if square_split(n, q) else (12, logn - 12)
+
+
+def xform_upg(n, q):
+    """kernels_dev.hpp xform_upg: polynomials per thread group of a standalone transform."""
+    return 2 if n <= 4096 and q < (1 << 32) else 1
+
+
+def rows_prio(case, cus=MI355X_CUS):
+    """launch_rows / rows_prio: the issue-prioritised fused product, u32 Plantard products only."""
+    logs = _logn(case.n)
+    if logs > 12 or arith_class(case.q) != "Arith32P" or case.word_bits != 32 or not case.batch:
+        return False
+    if case.prio:
+        return case.prio > 0
+    nt = 64 if logs == 10 else 256
+    per_block = nt // ((1 << logs) // 16)
+    blocks = (case.batch + per_block - 1) // per_block
+    return blocks * (nt // 64) <= (cus if case.prio_ok else 0) * 16
+
+
+def server_eligible(case):
+    """nttmul.cpp run_server: u32 host products of at most 1024 words per operand, Plantard
+    moduli, n <= 1024.  (Its twiddle-count condition never declines: the planner's tables hold
+    exactly n pairs.)"""
+    return (case.op == "multiply" and case.word_bits == 32 and case.n <= 1024
+            and case.batch * case.n <= 1024 and arith_class(case.q) == "Arith32P")
+
+
+def _product(case, cus):
+    a, io, w = arith_class(case.q), _io(case.word_bits), _io(native_bits(case.q))
+    logs, l1 = row_split(case.n, case.q)
+    if l1 == 0:
+        if a == "Arith32P" and logs == 12 and p3_fold_ok(case.q):
+            a = "Arith32P3"
+        prio = "true" if rows_prio(case, cus) else "false"
+        return [f"k_rows<{a},{io},{io},{logs},0,{prio}>"]
+    if square_split(case.n, case.q):
+        return [f"k_cols8<{a},{io},{w},0,2>", f"k_rows<{a},{w},{w},8,8,false>",
+                f"k_cols8<{a},{w},{io},1,1>"]
+    return [f"k_cols_fwd<{a},{io},{l1},2>", f"k_rows<{a},{w},{w},{logs},{l1},false>",
+            f"k_cols_inv<{a},{io},{l1}>"]
+
+
+def _transform(case):
+    a, io, w = arith_class(case.q), _io(case.word_bits), _io(native_bits(case.q))
+    logs, l1 = row_split(case.n, case.q)
+    inv = case.mode & 1
+    out = []
+    # run_device: the kernels run forward std2rev and inverse rev2std; the other two orders go
+    # through a bit-reversal into the scratch and one in place on the output
+    reorder = bool(inv) != bool(case.mode & 2)
+    if reorder:
+        out.append(f"k_bitrev<{io}>")
+    if l1 == 0:
+        out.append(f"k_xform<{a},{io},{io},{logs},0,{inv}>")
+    elif square_split(case.n, case.q):
+        out += ([f"k_cols8<{a},{io},{w},0,1>", f"k_xform<{a},{w},{io},8,8,0>"] if not inv else
+                [f"k_xform<{a},{io},{w},8,8,1>", f"k_cols8<{a},{w},{io},1,1>"])
+    else:
+        out += ([f"k_cols_fwd<{a},{io},{l1},1>", f"k_xform<{a},{w},{io},{logs},{l1},0>"] if not inv
+                else [f"k_xform<{a},{io},{w},{logs},{l1},1>", f"k_cols_inv<{a},{io},{l1}>"])
+    if reorder:
+        out.append(f"k_bitrev_inplace<{io}>")
+    return out
+
+
+def kernels_of(case, cus=MI355X_CUS):
+    """The kernel_keys `case` launches, in launch order."""
+    assert case.word_bits == 64 or case.q < (1 << 32), "io_ok refuses 32-bit words for q >= 2^32"
+    io = _io(case.word_bits)
+    if case.path == "server":
+        assert server_eligible(case)
+        return [f"k_server<Arith32P,{_logn(case.n)}>"]     # (validation runs on the host)
+    out = [f"k_check_range<{io}>"] if case.validate else []
+    if case.op == "multiply":
+        return out + _product(case, cus)
+    if case.op == "transform":
+        return out + _transform(case)
+    if case.op == "pointwise":
+        a = arith_class(case.q)
+        return out + [f"k_pointwise<{'Arith32' if a == 'Arith32P' else a},{io}>"]
+    if case.op == "fill":
+        return [f"k_fill<{io}>"]
+    raise ValueError(case.op)
+
+
+def product_keys(case, cus=MI355X_CUS):
+    """The product kernels of `case` without the range check."""
+    return [k for k in kernels_of(case, cus) if not k.startswith("k_check_range")]
+
+
+# Kernels the library holds that no call can launch: (regular expression over the kernel_key,
+# reason).  The first matching rule names a kernel's reason.
+UNREACHABLE = (
+    (r"k_\w+<Arith64,(u32(,.*)?|u64,u32,.*)>",
+     "Arith64 on u32 caller words: io_ok refuses 32-bit words for q >= 2^32"),
+    (r"k_cols_fwd<\w+,u\d+,5,2>|k_cols_inv<\w+,u\d+,5>|k_rows<\w+,u\d+,u\d+,11,5,false>",
+     "the 32 x 2048 split of n = 65536 sits behind NTTMUL_SPLIT16 == 5 (settled at 4)"),
+    (r"k_rows<Arith32P,u\d+,u\d+,12,0,(false|true)>",
+     "p3_fold_ok holds for every prime q < 2^31, so n = 4096 always takes Arith32P3"),
+    (r"k_cols_fwd<Arith64,u64,4,[12]>|k_cols_inv<Arith64,u64,4>|k_rows<Arith64,u64,u64,12,4,false>"
+     r"|k_xform<Arith64,u64,u64,12,4,[01]>",
+     "Arith64 at n = 65536 takes the square split (NTTMUL_C5_SQ), never 16 x 4096"),
+)
+
+
+# ---------------------------------------------------------------------------------------------
+# Case tables: the new modules
+# ---------------------------------------------------------------------------------------------
+
+# 1a. multi-pass products in 64-bit words on 32-bit moduli (tests/test_gpu_u64_words.py)
+U64_MULTIPASS = [(n, q) for n in MULTIPASS_N for q in (Q31HI, Q31LO, Q32)]
+# (the fused products in 64-bit words: test_random_prime_sweep runs n = 256, 1024 and 4096 only)
+U64_FUSED = [(n, q) for n in (256, 512, 1024, 2048, 4096) for q in (Q31HI, Q31LO, Q32)]
+# 1b. every transform mode and pointwise, every size, one modulus per class, both word widths
+# (negacyclic and cyclic), and three more moduli, negacyclic, at the sizes no other test runs
+XF_SWEEP = ([(n, q, cyclic) for n in ALL_N for q in CLASS_MODULI for cyclic in (False, True)]
+            + [(n, q, False) for n in (512, 2048, 32768) for q in (Q33, Q20, Q31LO)])
+XF_SWEEP_BATCHES = (3, 1)
+# 1c. the device path in 64-bit words
+U64_DEVICE = [(4096, Q31, 37), (8192, Q31HI, 5), (65536, Q32, 3)]
+# 1d. range validation
+VALIDATE = [(1024, Q31), (8192, Q32)]
+# 1e. the host path in several chunks
+U64_HOST_CHUNKS = (4096, Q31, 600)
+# 2. sub-batched transforms (scratch_mb = 1): n, q, word_bits, batch, modes
+SUBBATCH = [
+    (4096, Q31, 32, 129, (2, 1)),
+    (8192, Q31, 32, 65, XF_MODES),
+    (8192, Q31, 64, 65, (2, 3)),
+    (65536, Q62, 64, 5, XF_MODES),
+]
+SUBBATCH_PRODUCT = (8192, Q31, 64, 65)
+# 3. the resident server at every size it serves: (n, batch)
+SERVER_SHAPES = [(512, 1), (512, 2), (1024, 1), (256, 2), (256, 3), (256, 4)]
+SERVER_BITS = (14, 17, 20, 24, 28, 30, 31)
+SERVER_NAMED = (Q0, Q31, Q31HI, Q31LO)
+
+# ---------------------------------------------------------------------------------------------
+# Case tables: the parametrisations of tests/test_gpu_parity.py
+# ---------------------------------------------------------------------------------------------
+
+PARITY_MODULI = [Q31, Q30, Q32, Q62, Q31HI, Q31LO]
+PARITY_FUSED_N = [256, 512, 1024, 2048, 4096]          # test_random_vs_oracle
+PARITY_MULTIPASS_N = [8192, 16384, 32768, 65536]       # test_multipass_vs_oracle
+PARITY_XF_N = [256, 1024, 4096, 8192, 65536]           # test_transforms_vs_oracle
+PARITY_XF_MODULI = [Q31, Q30, Q32, Q62, Q31HI]
+PARITY_XF_MODES = [(256, Q30), (1024, Q31), (4096, Q31), (4096, Q32), (4096, Q62), (8192, Q30),
+                   (16384, Q32), (65536, Q62)]          # test_transform_modes_vs_oracle
+PARITY_PRIO = [(256, Q31), (512, Q31), (1024, Q31), (1024, Q30), (2048, Q31), (4096, Q31),
+               (4096, Q31HI)]                           # test_issue_priority_variants
+PARITY_SWEEP_N = [256, 1024, 4096]                     # test_random_prime_sweep, also in u64
+
+
+def prio_limit(n, cus=MI355X_CUS):
+    """The largest batch of n-word u32 Plantard products that still runs prioritised."""
+    return 16 * cus * max(1, 64 // (n // 16)) // max(1, n // 16 // 64)
+
+
+def parity_cases(cus=MI355X_CUS):
+    out = []
+    for q in PARITY_MODULI:
+        for n in PARITY_FUSED_N + PARITY_MULTIPASS_N:
+            out.append(Case("multiply", n, q, native_bits(q), 17, validate=n > 4096))
+    for n in PARITY_SWEEP_N:        # one prime of each class stands for the sweep's bit lengths
+        out += [Case("multiply", n, q, 64, 5) for q in (Q30, Q31, Q32, Q62)]
+    for n, q in PARITY_PRIO:
+        lim = prio_limit(n, cus)
+        out += [Case("multiply", n, q, 32, lim), Case("multiply", n, q, 32, lim + 17)]
+    out.append(Case("multiply", 1024, Q31, 32, 300, prio=-1))
+    out.append(Case("multiply", 1024, Q31, 32, 256, prio_ok=0))
+    for n in PARITY_XF_N:
+        for q in PARITY_XF_MODULI:
+            w = native_bits(q)
+            out += [Case("transform", n, q, w, 3, mode=0), Case("transform", n, q, w, 3, mode=3),
+                    Case("pointwise", n, q, w, 3)]
+    for n, q in PARITY_XF_MODES:
+        out += [Case("transform", n, q, native_bits(q), 2, mode=m) for m in XF_MODES]
+    out += [Case("fill", 4096, Q31, 32, 8), Case("fill", 65536, Q62, 64, 8)]
+    out += [Case("multiply", n, Q31, 32, 1024 // n, path="server") for n in (256, 512, 1024)]
+    return out
+
+
+def new_cases():
+    out = []
+    for n, q in U64_MULTIPASS:
+        out += [Case("multiply", n, q, 64, 3), Case("multiply", n, q, 32, 3)]
+    out += [Case("multiply", n, q, 64, 3) for n, q in U64_FUSED]
+    for n, q, _ in XF_SWEEP:
+        for w in word_options(q):
+            for batch in XF_SWEEP_BATCHES:
+                out += [Case("transform", n, q, w, batch, mode=m) for m in XF_MODES]
+                out.append(Case("pointwise", n, q, w, batch))
+    for n, q, batch in U64_DEVICE:
+        out += [Case("fill", n, q, 64, batch), Case("multiply", n, q, 64, batch),
+                Case("transform", n, q, 64, batch, mode=0), Case("pointwise", n, q, 64, batch),
+                Case("transform", n, q, 64, batch, mode=3), Case("transform", n, q, 64, batch, mode=2)]
+    for n, q in VALIDATE:
+        for w in (32, 64):
+            out += [Case("multiply", n, q, w, 2, validate=True),
+                    Case("transform", n, q, w, 2, mode=0, validate=True),
+                    Case("transform", n, q, w, 2, mode=3, validate=True),
+                    Case("pointwise", n, q, w, 2, validate=True)]
+    n, q, batch = U64_HOST_CHUNKS
+    out += [Case("multiply", n, q, 64, 256), Case("transform", n, q, 64, 256, mode=0),
+            Case("transform", n, q, 64, 256, mode=3)]
+    for n, q, w, batch, modes in SUBBATCH:
+        out += [Case("transform", n, q, w, batch, mode=m) for m in modes]
+    n, q, w, batch = SUBBATCH_PRODUCT
+    out.append(Case("multiply", n, q, w, batch))
+    for n, batch in SERVER_SHAPES:
+        out += [Case("multiply", n, q, 32, batch, path="server") for q in SERVER_NAMED]
+    return out
+
+
+def all_cases(cus=MI355X_CUS):
+    return parity_cases(cus) + new_cases()

@@ -16,15 +16,12 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-Q0 = 12289
-Q31 = 2013265921            # 15 * 2^27 + 1, the benchmark modulus
-Q30 = 1073479681            # < 2^30
-Q32 = 4293918721            # 0xFFF00001, full 32-bit word
-Q62 = 0x3FFFFFFFFFE80001    # 62-bit, 2^17 | q - 1
-# the ends of the Arith32 range (2^30 < q < 2^31), where the typed butterflies' bounds are
-# tightest (signed Montgomery in (-0.75 q, 0.75 q), unsigned in [0, 2q)); 2^17 | q - 1
-Q31HI = 2147352577
-Q31LO = 1073872897
+# the moduli and the parametrisations below live in tests/dispatch_cases.py, whose ledger test
+# (tests/test_kernel_ledger.py) names the kernels each case launches.  Q31 is the benchmark
+# modulus; Q31HI and Q31LO are the ends of the Arith32 range (2^30 < q < 2^31), where the typed
+# butterflies' bounds are tightest (signed Montgomery in (-0.75 q, 0.75 q), unsigned in [0, 2q))
+import dispatch_cases as D
+from dispatch_cases import Q0, Q30, Q31, Q31HI, Q31LO, Q32, Q62
 
 
 @pytest.fixture(scope="module")
@@ -118,8 +115,8 @@ def test_schoolbook_bigint_golden(golden_dir, torch_cuda):
             assert np.array_equal(c64, g[key + "_c"]), key
 
 
-@pytest.mark.parametrize("n", [256, 512, 1024, 2048, 4096])
-@pytest.mark.parametrize("q", [Q31, Q30, Q32, Q62, Q31HI, Q31LO])
+@pytest.mark.parametrize("n", D.PARITY_FUSED_N)
+@pytest.mark.parametrize("q", D.PARITY_MODULI)
 def test_random_vs_oracle(n, q, torch_cuda):
     """Ragged batch sizes (partial blocks) against the restated psi-merged product."""
     P = O.Plan(n, q)
@@ -161,7 +158,7 @@ def _random_primes(bits_list, step_log, seed):
 _SWEEP_BITS = [14, 16, 20, 24, 28, 29, 30, 31, 31, 32, 32, 33, 36, 44, 52, 60, 61, 62, 62]
 
 
-@pytest.mark.parametrize("n", [256, 1024, 4096])
+@pytest.mark.parametrize("n", D.PARITY_SWEEP_N)
 def test_random_prime_sweep(n, torch_cuda):
     """Random NTT-friendly primes of every bit length 14..62 (seeded, 2n | q - 1): a ragged
     batch of random and extreme (all q - 1) operands, every product against the restated
@@ -195,8 +192,8 @@ def test_random_prime_sweep_multipass(n, torch_cuda):
             assert np.array_equal(c[i], P.product_merged(a[i], b[i])), (n, q, i)
 
 
-@pytest.mark.parametrize("n", [8192, 16384, 32768, 65536])
-@pytest.mark.parametrize("q", [Q31, Q30, Q32, Q62, Q31HI, Q31LO])
+@pytest.mark.parametrize("n", D.PARITY_MULTIPASS_N)
+@pytest.mark.parametrize("q", D.PARITY_MODULI)
 def test_multipass_vs_oracle(n, q, torch_cuda):
     """n > 4096: column pass + fused rows + inverse column pass, ragged batch of 3 (and 17 at
     n = 8192) against the restated reference product (OpenMP batch) and evaluation at roots."""
@@ -285,8 +282,7 @@ def test_full_size_device_path(n, q, word_bits, batch, scratch_mb, torch_cuda):
     assert _check_whole_batch(n, q, word_bits, 0, batch, a, b, c) == batch
 
 
-@pytest.mark.parametrize("n,q", [(256, Q31), (512, Q31), (1024, Q31), (1024, Q30), (2048, Q31),
-                                 (4096, Q31), (4096, Q31HI)])
+@pytest.mark.parametrize("n,q", D.PARITY_PRIO)
 def test_issue_priority_variants(n, q, torch_cuda):
     """The fused product has two launch forms (kernels.hip rows_prio): batches of at most 4 waves
     per SIMD run k_rows<..., PRIO = true> (issue priority lowered as each wave completes its
@@ -546,8 +542,8 @@ def test_transforms_ref256_golden(golden_dir, torch_cuda):
     assert np.array_equal(ctx.inverse(g["x"]), g["inverse"])
 
 
-@pytest.mark.parametrize("n", [256, 1024, 4096, 8192, 65536])
-@pytest.mark.parametrize("q", [Q31, Q30, Q32, Q62, Q31HI])
+@pytest.mark.parametrize("n", D.PARITY_XF_N)
+@pytest.mark.parametrize("q", D.PARITY_XF_MODULI)
 def test_transforms_vs_oracle(n, q, torch_cuda):
     P = O.Plan(n, q)
     ctx = _ctx(n, q)
@@ -1018,8 +1014,7 @@ def _xf_expected(P, x, mode, cyclic, n, q):
 
 
 @pytest.mark.parametrize("cyclic", [False, True])
-@pytest.mark.parametrize("n,q", [(256, Q30), (1024, Q31), (4096, Q31), (4096, Q32), (4096, Q62),
-                                 (8192, Q30), (16384, Q32), (65536, Q62)])
+@pytest.mark.parametrize("n,q", D.PARITY_XF_MODES)
 def test_transform_modes_vs_oracle(n, q, cyclic, torch_cuda):
     """nttmul_transform_*: every (direction, order, scaling) equals the reference's loop of the
     same name (restated in the oracle; pinned by test_oracle.py::test_wrappers_golden)."""
