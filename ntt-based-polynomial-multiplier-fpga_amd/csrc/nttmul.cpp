@@ -28,6 +28,10 @@
 #include "copy_pool.hpp"
 #include "launch.hpp"
 #include "nttmul.h"
+#ifdef NTTMUL_MAC
+#include "mac.hpp"
+#include "nttmul_mac.h"
+#endif
 
 #include "planner.hpp"
 
@@ -1111,6 +1115,102 @@ void mulntt256_ct_rev2std(int32_t *a) { transform256(a, 0, kFwdR2S); }
 void mulntt256_ct_std2rev(int32_t *a) { transform256(a, 0, kFwdS2R); }
 void inttmul256_gs_rev2std(int32_t *a) { transform256(a, 0, kInvR2S); }
 void inttmul256_gs_std2rev(int32_t *a) { transform256(a, 0, kInvS2R); }
+
+#ifdef NTTMUL_MAC
+// include/nttmul_mac.h (lib/libnttmul_mac.so only): products and dot products against NTT-domain
+// operands.  These calls leave prod_s / last_prod alone: the issue-priority rule and
+// nttmul_last_kernel_name describe plain products only.
+
+// what is decided before any device access
+static int mac_args(const nttmul_ctx *ctx, const void *c, const void *a, const void *b_hat,
+                    size_t batch, uint32_t terms, int word_bits) {
+  if (!ctx || !terms || !io_ok(ctx, word_bits)) return NTTMUL_EINVAL;
+  if (batch && (!c || !a || !b_hat)) return NTTMUL_EINVAL;
+  return ctx->plan.logn > 12 ? NTTMUL_EUNSUPPORTED : NTTMUL_OK;
+}
+
+// on d (the current device), stream s
+static int mac_run(nttmul_ctx *ctx, DevState &d, void *c, const void *a, const void *b_hat,
+                   size_t batch, uint32_t terms, int shared, int word_bits, hipStream_t s) {
+  if (!batch) return NTTMUL_OK;
+  const Plan &P = ctx->plan;
+  const size_t atotal = batch * terms * P.n, btotal = shared ? (size_t)terms * P.n : atotal;
+  if (ctx->flags & NTTMUL_FLAG_VALIDATE) {
+    HIP_TRY(ctx, hipMemsetAsync(d.flag, 0, sizeof(int), s));
+    HIP_TRY(ctx, launch_check_range(a, a, P.q, atotal, word_bits, d.flag, s));
+    HIP_TRY(ctx, launch_check_range(b_hat, b_hat, P.q, btotal, word_bits, d.flag, s));
+    int bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, d.flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (bad) {
+      set_err(ctx, "input coefficient >= q");
+      return NTTMUL_ERANGE;
+    }
+  }
+  HIP_TRY(ctx, launch_mac(tables_for(ctx, d), a, b_hat, c, batch, terms, shared, word_bits, s));
+  return NTTMUL_OK;
+}
+
+int nttmul_mac_ntt_device(nttmul_ctx *ctx, void *c, const void *a, const void *b_hat,
+                          size_t batch, uint32_t terms, int shared, int word_bits, int dev,
+                          void *stream) {
+  if (const int st = mac_args(ctx, c, a, b_hat, batch, terms, word_bits)) return st;
+  DevState *d = find_dev(ctx, dev);
+  if (!d) return NTTMUL_ENODEV;
+  if (const int st = server_quiesce(ctx)) return st;
+  DeviceGuard guard;
+  HIP_TRY(ctx, hipSetDevice(d->id));
+  return mac_run(ctx, *d, c, a, b_hat, batch, terms, shared, word_bits, (hipStream_t)stream);
+}
+
+// Host buffers: dev[0], device buffers owned by the call, the device path, copy back, synchronise
+static int mac_host(nttmul_ctx *ctx, void *c, const void *a, const void *b_hat, size_t batch,
+                    uint32_t terms, int shared, int word_bits) {
+  if (const int st = mac_args(ctx, c, a, b_hat, batch, terms, word_bits)) return st;
+  if (!batch) return NTTMUL_OK;
+  if (const int st = server_quiesce(ctx)) return st;
+  DevState &d = ctx->dev[0];
+  DeviceGuard guard;
+  HIP_TRY(ctx, hipSetDevice(d.id));
+  const size_t poly = (size_t)ctx->plan.n * (word_bits / 8);
+  const size_t bytes[3] = {batch * poly, batch * terms * poly, (shared ? 1 : batch) * terms * poly};
+  void *buf[3] = {nullptr, nullptr, nullptr};  // c, a, b_hat
+  int st = NTTMUL_OK;
+  const auto step = [&](hipError_t e, const char *what) {
+    if (!st && e != hipSuccess) st = fail(ctx, e, what);
+    return !st;
+  };
+  for (int i = 0; i < 3 && !st; i++) step(hipMalloc(&buf[i], bytes[i]), "mac host buffers");
+  if (!st && step(hipMemcpyAsync(buf[1], a, bytes[1], hipMemcpyHostToDevice, d.stream), "mac copy a") &&
+      step(hipMemcpyAsync(buf[2], b_hat, bytes[2], hipMemcpyHostToDevice, d.stream), "mac copy b_hat")) {
+    st = mac_run(ctx, d, buf[0], buf[1], buf[2], batch, terms, shared, word_bits, d.stream);
+    if (!st) step(hipMemcpyAsync(c, buf[0], bytes[0], hipMemcpyDeviceToHost, d.stream), "mac copy c");
+  }
+  // (also after a failure: nothing of this call may still run when its buffers go)
+  const hipError_t e = hipStreamSynchronize(d.stream);
+  step(e, "mac synchronise");
+  for (void *p : buf)
+    if (p) (void)hipFree(p);
+  return st;
+}
+
+int nttmul_mac_ntt_u32(nttmul_ctx *ctx, uint32_t *c, const uint32_t *a, const uint32_t *b_hat,
+                       size_t batch, uint32_t terms, int shared) {
+  return mac_host(ctx, c, a, b_hat, batch, terms, shared, 32);
+}
+int nttmul_mac_ntt_u64(nttmul_ctx *ctx, uint64_t *c, const uint64_t *a, const uint64_t *b_hat,
+                       size_t batch, uint32_t terms, int shared) {
+  return mac_host(ctx, c, a, b_hat, batch, terms, shared, 64);
+}
+
+int nttmul_mac_kernel_name(const nttmul_ctx *ctx, int word_bits, char *buf, size_t cap) {
+  if (!ctx || !io_ok(ctx, word_bits) || (cap && !buf)) return NTTMUL_EINVAL;
+  std::string name;
+  if (describe_mac(tables_for(ctx, ctx->dev[0]), word_bits, &name) != hipSuccess)
+    return NTTMUL_EUNSUPPORTED;
+  return copy_name(buf, cap, name);
+}
+#endif
 
 #ifdef NTTMUL_CLOCK_STAMPS
 // include/nttmul_diag.h (lib/libnttmul_diag.so only)

@@ -19,7 +19,10 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul.so")
 # the diagnostic build (include/nttmul_diag.h): same kernels plus in-kernel clock stamps
 DIAG_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_diag.so")
+# products against NTT-domain operands (include/nttmul_mac.h): the same ABI and kernels plus k_mac
+MAC_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_mac.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul.h")
+MAC_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_mac.h")
 
 NTTMUL_OK = 0
 NTTMUL_EINVAL = -1
@@ -633,6 +636,78 @@ class Context:
         args = [_dev_arg(t, count, self.n, word_bits, dev) for t in (a, b)]
         self._check(self._lib.nttmul_fill_random_device(self._h, *args, p0, count, seed,
                                                         word_bits, dev, stream or None))
+
+
+# ---- products against NTT-domain operands (include/nttmul_mac.h) ---------------------------------
+
+_MAC_LIB: Optional[ctypes.CDLL] = None
+
+
+def load_mac_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_mac.so (include/nttmul_mac.h): the ABI and kernels of libnttmul.so plus
+    the fused multiply-accumulate against NTT-domain operands.  load_library() is unaffected."""
+    global _MAC_LIB
+    if _MAC_LIB is not None:
+        return _MAC_LIB
+    if not os.path.exists(MAC_LIB_PATH):
+        raise ImportError(f"{MAC_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
+    lib = _bind(ctypes.CDLL(MAC_LIB_PATH))
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    lib.nttmul_mac_ntt_device.argtypes = [vp, vp, vp, vp, sz, u32, i32, i32, i32, vp]
+    for w in ("u32", "u64"):
+        getattr(lib, f"nttmul_mac_ntt_{w}").argtypes = [vp, vp, vp, vp, sz, u32, i32]
+    lib.nttmul_mac_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
+    _MAC_LIB = lib
+    return lib
+
+
+def mac_exported_symbols() -> list:
+    """Function names declared in include/nttmul_mac.h."""
+    import re
+    return sorted(set(re.findall(r"^\s*int\s+(nttmul_mac_\w+)\s*\(", open(MAC_HEADER_PATH).read(), re.M)))
+
+
+class MacContext(Context):
+    """A Context created through lib/libnttmul_mac.so: every Context method, plus
+    c[p] = INTT(sum_t NTT(a[p][t]) o b_hat[p or 0][t]) for n <= 4096 (include/nttmul_mac.h)."""
+
+    def __init__(self, n: int, q: int, **kw):
+        super().__init__(n, q, _lib=load_mac_library(), **kw)
+
+    def mac_kernel_name(self, word_bits: int = 0) -> str:
+        """nttmul_mac_kernel_name, e.g. "k_mac<Arith32P,u32,u32,12>"."""
+        word_bits = word_bits or (32 if self.q < (1 << 32) else 64)
+        buf = ctypes.create_string_buffer(256)
+        st = self._lib.nttmul_mac_kernel_name(self._h, word_bits, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def mac_ntt_device(self, c, a, b_hat, batch: int, terms: int, word_bits: int,
+                       shared: bool = False, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        a [batch][terms][n], b_hat [batch][terms][n] ([terms][n] when shared), c [batch][n]."""
+        dev = self.first_dev if dev is None else dev
+        counts = (batch, batch * terms, terms if shared else batch * terms)
+        args = [_dev_arg(t, k, self.n, word_bits, dev) for t, k in zip((c, a, b_hat), counts)]
+        self._check(self._lib.nttmul_mac_ntt_device(self._h, *args, batch, terms, int(shared),
+                                                    word_bits, dev, stream or None))
+
+    def mac_ntt(self, a, b_hat, shared: bool = False, dtype=None) -> np.ndarray:
+        """Host arrays: a of shape [batch, terms, n]; b_hat of a's shape, or [terms, n] when
+        shared.  Returns c of shape [batch, n]."""
+        dtype = dtype or self.io_dtype
+        a = np.ascontiguousarray(a, dtype=dtype)
+        b_hat = np.ascontiguousarray(b_hat, dtype=dtype)
+        if a.ndim != 3 or a.shape[-1] != self.n or a.shape[1] == 0:
+            raise ValueError("a must have shape [batch, terms, n] with terms > 0")
+        if b_hat.shape != (a.shape[1:] if shared else a.shape):
+            raise ValueError("b_hat must have a's shape, or [terms, n] when shared")
+        c = np.empty((a.shape[0], self.n), dtype=dtype)
+        fn = self._lib.nttmul_mac_ntt_u32 if dtype == np.uint32 else self._lib.nttmul_mac_ntt_u64
+        self._check(fn(self._h, c.ctypes.data, a.ctypes.data, b_hat.ctypes.data, a.shape[0],
+                       a.shape[1], int(shared)))
+        return c
 
 
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------

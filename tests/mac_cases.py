@@ -1,0 +1,90 @@
+"""Case tables of tests/test_gpu_mac.py and a pure-Python mirror of the dispatch behind
+include/nttmul_mac.h (csrc/mac.hip mac_dispatch): plain data and arithmetic, no GPU, no library.
+
+tests/test_mac_ledger.py holds the mirror against the cross-compiled lib/libnttmul_mac.so (the
+kernels it holds beyond libnttmul.so's are exactly the ones the mirror names over these cases);
+test_gpu_mac.py::test_mirror_agrees_with_the_library_dispatch anchors it on the GPU to the
+library's own dry run (nttmul_mac_kernel_name)."""
+from collections import namedtuple
+
+import dispatch_cases as D
+
+MAC_N = (256, 512, 1024, 2048, 4096)
+# a partial last block at every n: 256 / (n / 16) = 16, 8, 4, 2, 1 polynomials per block
+BATCH = 17
+# one modulus per arithmetic class at every n; the Plantard class rotates through its three
+PLANTARD_AT = {256: D.Q31HI, 512: D.Q31LO, 1024: D.Q20, 2048: D.Q31HI, 4096: D.Q31LO}
+TERMS = (1, 3)
+TERMS_LONG = 7              # added at the smallest and the largest n
+LONG_N = (256, 4096)
+
+# op "mac": one nttmul_mac_ntt_* call
+Case = namedtuple("Case", "n q word_bits terms shared batch validate", defaults=(BATCH, False))
+
+
+def moduli_at(n):
+    return (PLANTARD_AT[n], D.Q32, D.Q62)
+
+
+def terms_at(n):
+    return TERMS + ((TERMS_LONG,) if n in LONG_N else ())
+
+
+def parity_cases():
+    """Test 1: every n, one modulus per class, every word width, terms, shared and per-batch."""
+    return [Case(n, q, w, t, s) for n in MAC_N for q in moduli_at(n) for w in D.word_options(q)
+            for t in terms_at(n) for s in (False, True)]
+
+
+# Test 2: worst-case ranges (every word q - 1) at terms = 7; the 31-bit entry None stands for
+# 2^31 - 1 where it is a usable prime for n, else the largest prime below 2^31 with 2n | q - 1
+RANGE_N = LONG_N
+RANGE_MODULI = (D.Q31HI, None, D.Q32, D.Q62)
+RANGE_BATCH = 3
+# Test 3: cyclic contexts (n, q, omega; q None: the largest 31-bit prime with n | q - 1)
+CYCLIC = ((256, 12289, 8595), (1024, None, 0))
+CYCLIC_TERMS = 2
+# Test 4: the device-path rules
+RULES = (1024, D.Q31, 32)
+VALIDATE = (512, D.Q31HI, 32)
+UNSUPPORTED_N = 8192
+# Test 5: host forms
+HOST = (1024, 5, 3)         # n, batch, terms
+
+
+def all_cases():
+    out = parity_cases()
+    out += [Case(n, q, D.native_bits(q), TERMS_LONG, s, RANGE_BATCH)
+            for n in RANGE_N for q in RANGE_MODULI if q for s in (False, True)]
+    n, q, w = RULES
+    out += [Case(n, q, w, 2, s, 5) for s in (False, True)]
+    n, q, w = VALIDATE
+    out.append(Case(n, q, w, 2, False, 3, validate=True))
+    n, batch, terms = HOST
+    out += [Case(n, q, w, terms, False, batch) for q in moduli_at(n) for w in D.word_options(q)]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# The mirror
+# ---------------------------------------------------------------------------------------------
+
+def mac_kernel(n, q, word_bits):
+    """mac.hip mac_dispatch: the class follows q alone (plain Arith32P at n = 4096 too), one
+    kernel per (class, caller word, n); shared operands are a stride of the same kernel."""
+    assert word_bits == 64 or q < (1 << 32), "io_ok refuses 32-bit words for q >= 2^32"
+    assert n & (n - 1) == 0 and 256 <= n <= 4096, "n > 4096 is NTTMUL_EUNSUPPORTED"
+    io = "u32" if word_bits == 32 else "u64"
+    return f"k_mac<{D.arith_class(q)},{io},{io},{n.bit_length() - 1}>"
+
+
+def kernels_of(case):
+    """The kernel_keys `case` launches, in launch order (the range check runs once per operand)."""
+    io = "u32" if case.word_bits == 32 else "u64"
+    return ([f"k_check_range<{io}>"] * 2 if case.validate else []) + \
+        [mac_kernel(case.n, case.q, case.word_bits)]
+
+
+# Kernels of libnttmul_mac.so beyond libnttmul.so's that no call can launch: (regular expression
+# over the kernel_key, reason).  None: mac.hip instantiates only what mac_dispatch reaches.
+UNREACHABLE = ()
