@@ -1,0 +1,47 @@
+// rns.hpp — internal interface between the host entry points of include/nttmul_rns.h (rns.cpp)
+// and the launchers of rns.hip.  lib/libnttmul_rns.so only.
+#pragma once
+#include "launch.hpp"
+
+namespace nttmul {
+
+// The kernel families of an RNS context.  Each reads its own per-device table of KParams<A>, one
+// entry per limb, because the scale folded into the last inverse stage differs:
+//   kRnsProduct    F 2^D  (kernels_dev.hpp product_params; D = 3 at n = 4096 with 32-bit words)
+//   kRnsTransform  F      (make_params: the mac's inverse; the forward transform reads no scale)
+//   kRnsInverse    n^-1   (the fi / wfi pairs of the standalone inverse)
+enum RnsFamily { kRnsProduct = 0, kRnsTransform = 1, kRnsInverse = 2, kRnsFamilies = 3 };
+enum RnsOp { kRnsMultiply = 0, kRnsForward = 1, kRnsInverseOp = 2, kRnsMac = 3 };
+
+// Per-device view of an RNS context: what a launch needs (pointers are device memory).
+struct RnsTables {
+  uint32_t logn = 0, limbs = 0;
+  int word_bits = 0;                 // 32: every q_l < 2^31 (Arith32P / Arith32P3), 64: Arith64
+  const void *tab[kRnsFamilies] = {nullptr, nullptr, nullptr};  // KParams<A>[limbs] each
+  // the limbs' twiddle (value, companion) pairs in one allocation: fw of limb l at pair 2 l n,
+  // iw at pair (2 l + 1) n (the pointers the table entries hold as well)
+  const void *tw = nullptr;
+  const uint64_t *q = nullptr;       // the moduli, [limbs] (range check)
+};
+
+// bytes of one table entry for words of word_bits (every class of a word size has one layout)
+size_t rns_entry_bytes(int word_bits);
+// The entry of family `fam` for one limb, from that limb's LaunchTables (fw / iw are the limb's
+// device twiddle tables), written to host memory at dst.  hipErrorNotSupported for a modulus the
+// family's arithmetic class does not take (Arith32P3's fold at n = 4096: arith_select.hpp
+// p3_fold_ok, true for every q < 2^31 and checked all the same).
+hipError_t rns_fill_entry(const LaunchTables &T, int fam, void *dst);
+
+// One launch over a [batch][limbs][n] operand set on stream s (rns_dev.hpp), grid = (blocks over
+// the batch, limbs).  op kRnsMultiply: c = a * b;  kRnsForward / kRnsInverseOp: c = transform(a),
+// c == a allowed;  kRnsMac: a [batch][terms][limbs][n], b = b_hat [batch or 1][terms][limbs][n].
+hipError_t launch_rns(const RnsTables &T, int op, void *c, const void *a, const void *b,
+                      size_t batch, uint32_t terms, int shared, hipStream_t s);
+// The kernel launch_rns launches for (T, op), as "k_rns_rows<Arith32P3,u32,12>": the dry run of
+// the launching statement itself (kernels_dev.hpp Emit)
+hipError_t describe_rns(const RnsTables &T, int op, std::string *out);
+// *bad |= 1 when a word i < total of a is >= q[(i / n) mod limbs]
+hipError_t launch_rns_check(const RnsTables &T, const void *a, size_t total, int *bad,
+                            hipStream_t s);
+
+}  // namespace nttmul

@@ -1,0 +1,445 @@
+"""GPU parity of the limb-aware calls (include/nttmul_rns.h, lib/libnttmul_rns.so, csrc/rns_dev.hpp
+k_rns_rows / k_rns_xform / k_rns_mac): one launch over [batch][limbs][n] operands.
+
+Everything is bit-exact.  Expected products come from the CPU oracle per (polynomial, limb),
+summed in Python integers for the mac; where the oracle has no counterpart (the forward
+transform's output order, arbitrary canonical b_hat) they come from a plain nttmul.Context(n, q_l)
+of lib/libnttmul.so, which is not the code under test.  Inputs are the oracle's counter-based
+fill per limb, so every limb's words are canonical for its own modulus.  Shapes are the smallest
+at which the kernels can go wrong (tests/rns_cases.py): every n has its own register layouts and
+exchanges, batch 17 leaves a partial last workgroup and a half-empty transform pair."""
+import functools
+
+import numpy as np
+import pytest
+
+import nttmul
+import rns_cases as R
+from oracle import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+CLASSES = {"u32": R.BASIS32, "u64": R.BASIS64}
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch
+
+
+def _dt(bits):
+    return np.uint32 if bits == 32 else np.uint64
+
+
+def _to_dev(torch, x, bits):
+    x = np.ascontiguousarray(x, dtype=_dt(bits))
+    return torch.from_numpy(x.view(np.int32 if bits == 32 else np.int64).reshape(-1)).cuda()
+
+
+def _from_dev(t, bits, shape):
+    return t.cpu().numpy().view(_dt(bits)).reshape(shape).astype(np.uint64)
+
+
+def _call(torch, ctx, op, a, b=None, shared=False, stream=0, in_place=False):
+    """One device call on numpy operands; returns (result, operands after the call)."""
+    bits = ctx.word_bits
+    batch = a.shape[0]
+    da = _to_dev(torch, a, bits)
+    db = None if b is None else _to_dev(torch, b, bits)
+    dc = da if in_place else torch.empty(batch * ctx.limbs * ctx.n, dtype=da.dtype, device="cuda")
+    if op == "multiply":
+        ctx.multiply_device(dc, da, db, batch, stream=stream)
+    elif op == "forward":
+        ctx.forward_device(dc, da, batch, stream=stream)
+    elif op == "inverse":
+        ctx.inverse_device(dc, da, batch, stream=stream)
+    else:
+        ctx.mac_ntt_device(dc, da, db, batch, a.shape[1], shared=shared, stream=stream)
+    torch.cuda.synchronize()
+    after = [_from_dev(da, bits, a.shape)] + ([] if b is None else [_from_dev(db, bits, b.shape)])
+    return _from_dev(dc, bits, (batch, ctx.limbs, ctx.n)), after
+
+
+def _sum_mod(rows, q):
+    """sum of uint64 arrays mod q, in Python integers."""
+    acc = rows[0].astype(object)
+    for r in rows[1:]:
+        acc = acc + r.astype(object)
+    return (acc % q).astype(np.uint64)
+
+
+def _tmax(n):
+    return max(R.terms_at(n))
+
+
+@functools.lru_cache(maxsize=None)
+def _limb_operands(n, q, batch, terms, p0=40):
+    a, b = O.fill_inputs(n, q, p0, batch * terms)
+    a.setflags(write=False)
+    b.setflags(write=False)
+    return a.reshape(batch, terms, n), b.reshape(batch, terms, n)
+
+
+def _operands(n, moduli, batch, terms, p0=40):
+    """a, b of shape [batch, terms, limbs, n], limb l canonical for moduli[l]."""
+    per = [_limb_operands(n, q, batch, terms, p0) for q in moduli]
+    return (np.ascontiguousarray(np.stack([x[0] for x in per], axis=2)),
+            np.ascontiguousarray(np.stack([x[1] for x in per], axis=2)))
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_products(n, q):
+    """prod[s][p][t] = oracle product of a[p][t] with b[p][t] (s = 0) or b[0][t] (s = 1, the
+    shared operand) of one limb, computed once per (n, q) and shared by every test."""
+    P = O.Plan(n, q)
+    batch, terms = R.BATCH, _tmax(n)
+    a, b = _limb_operands(n, q, batch, terms)
+    out = np.zeros((2, batch, terms, n), dtype=np.uint64)
+    for p in range(batch):
+        for t in range(terms):
+            out[0, p, t] = P.product_merged(a[p, t], b[p, t])
+            out[1, p, t] = out[0, p, t] if p == 0 else P.product_merged(a[p, t], b[0, t])
+    out.setflags(write=False)
+    return out
+
+
+def _expected_mac(n, moduli, terms, shared):
+    """[BATCH, limbs, n]: per limb, the sum over t < terms of the oracle's products."""
+    return np.stack([_sum_mod([_oracle_products(n, q)[int(shared)][:, t] for t in range(terms)], q)
+                     for q in moduli], axis=1)
+
+
+_PLAIN = {}
+
+
+def _plain(n, q):
+    """A plain context of lib/libnttmul.so (kept for the module: a handful of (n, q))."""
+    if (n, q) not in _PLAIN:
+        _PLAIN[n, q] = nttmul.Context(n, q)
+    return _PLAIN[n, q]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _close_plain_contexts():
+    yield
+    while _PLAIN:
+        _PLAIN.popitem()[1].close()
+
+
+def _plain_per_limb(op, n, moduli, x, dtype):
+    """op of plain contexts on x [batch, limbs, n], limb by limb."""
+    return np.stack([getattr(_plain(n, q), op)(np.ascontiguousarray(x[:, l]), dtype=dtype)
+                     for l, q in enumerate(moduli)], axis=1).astype(np.uint64)
+
+
+def _plain_forward_terms(n, moduli, b, dtype):
+    """forward of b [batch, terms, limbs, n] per limb, by plain contexts."""
+    batch, terms = b.shape[:2]
+    flat = _plain_per_limb("forward", n, moduli, b.reshape(batch * terms, len(moduli), n), dtype)
+    return flat.reshape(b.shape)
+
+
+def _differ(got, want):
+    bad = np.argwhere((got != want).any(axis=-1))
+    return f"{len(bad)} (polynomial, limb) pairs differ, first {bad[0] if len(bad) else None}"
+
+
+PARAMS = [(n, c) for n in R.RNS_N for c in CLASSES]
+
+
+def _bases(n, cls):
+    return [m for m in R.bases_at(n) if R.word_bits(m) == R.word_bits(CLASSES[cls])]
+
+
+# ---------------------------------------------------------------------------------------------
+# 1. products
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n,cls", PARAMS)
+def test_product_parity_with_the_oracle(n, cls, torch_cuda):
+    """Every n, L in {1, 3} (and five 32-bit limbs at two n), batch 17 and 1: each (p, l) equals
+    the oracle's product mod q_l; operands unchanged; the L = 1 result equals a plain
+    context's."""
+    for moduli in _bases(n, cls):
+        ctx = nttmul.RnsContext(n, moduli)
+        assert (ctx.limbs, ctx.word_bits) == (len(moduli), R.word_bits(moduli))
+        assert ctx.kernel_name("multiply") == R.rns_kernel("multiply", n, moduli)
+        a, b = _operands(n, moduli, R.BATCH, _tmax(n))
+        a, b = np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(b[:, 0])
+        want = np.stack([_oracle_products(n, q)[0][:, 0] for q in moduli], axis=1)
+        for batch in (R.BATCH, 1):
+            got, after = _call(torch_cuda, ctx, "multiply", a[:batch], b[:batch])
+            assert np.array_equal(got, want[:batch]), (moduli, batch, _differ(got, want[:batch]))
+            assert np.array_equal(after[0], a[:batch]) and np.array_equal(after[1], b[:batch])
+        if len(moduli) == 1:
+            plain = _plain(n, moduli[0]).multiply(a[:, 0], b[:, 0], dtype=ctx.io_dtype)
+            assert np.array_equal(got, plain[:1, None].astype(np.uint64))
+        ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 2. transforms
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n,cls", PARAMS)
+def test_transforms_equal_plain_contexts_per_limb(n, cls, torch_cuda):
+    """forward and inverse against plain contexts of (n, q_l), limb by limb (output order and
+    range included), batch 17 (a half-empty last pair on 32-bit words) and 1; then
+    inverse(forward(a)) == a with both calls in place."""
+    for moduli in _bases(n, cls):
+        ctx = nttmul.RnsContext(n, moduli)
+        dt = ctx.io_dtype
+        a, _ = _operands(n, moduli, R.BATCH, _tmax(n))
+        a = np.ascontiguousarray(a[:, 0])
+        fwd = _plain_per_limb("forward", n, moduli, a, dt)
+        inv = _plain_per_limb("inverse", n, moduli, a, dt)
+        for op, want in (("forward", fwd), ("inverse", inv)):
+            assert ctx.kernel_name(op) == R.rns_kernel(op, n, moduli)
+            for batch in (R.BATCH, 1):
+                got, after = _call(torch_cuda, ctx, op, a[:batch])
+                assert np.array_equal(got, want[:batch]), (op, moduli, batch, _differ(got, want[:batch]))
+                assert np.array_equal(after[0], a[:batch])
+        hat, after = _call(torch_cuda, ctx, "forward", a, in_place=True)
+        assert np.array_equal(hat, fwd) and np.array_equal(after[0], fwd)
+        back, _ = _call(torch_cuda, ctx, "inverse", hat, in_place=True)
+        assert np.array_equal(back, a), (moduli, _differ(back, a))
+        ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 3. multiply-accumulate against NTT-domain operands
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n,cls", PARAMS)
+def test_mac_parity_with_the_oracle(n, cls, torch_cuda):
+    """terms 1 and 3 (7 at n = 256 and 4096), shared and per-batch b_hat = forward(b) by plain
+    contexts, batch 17 (and once batch 1): each (p, l) equals the sum of the oracle's products
+    mod q_l."""
+    for moduli in _bases(n, cls):
+        ctx = nttmul.RnsContext(n, moduli)
+        assert ctx.kernel_name("mac") == R.rns_kernel("mac", n, moduli)
+        a, b = _operands(n, moduli, R.BATCH, _tmax(n))
+        b_hat = _plain_forward_terms(n, moduli, b, ctx.io_dtype)
+        for terms in R.terms_at(n):
+            for shared in (False, True):
+                ai = np.ascontiguousarray(a[:, :terms])
+                bi = np.ascontiguousarray(b_hat[0, :terms] if shared else b_hat[:, :terms])
+                got, after = _call(torch_cuda, ctx, "mac", ai, bi, shared=shared)
+                want = _expected_mac(n, moduli, terms, shared)
+                assert np.array_equal(got, want), (moduli, terms, shared, _differ(got, want))
+                assert np.array_equal(after[0], ai) and np.array_equal(after[1], bi)
+        terms = _tmax(n)                                    # and a batch of one
+        got, _ = _call(torch_cuda, ctx, "mac", a[:1, :terms], b_hat[:1, :terms])
+        assert np.array_equal(got, _expected_mac(n, moduli, terms, False)[:1]), moduli
+        ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 4. worst-case ranges
+# ---------------------------------------------------------------------------------------------
+
+def _existing_mac(n, moduli, a, b_hat, shared, dt):
+    """Per limb inverse((sum_t pointwise(forward(a_t), b_hat_t)) mod q), the sum on the host:
+    three calls of a plain context."""
+    out = []
+    for l, q in enumerate(moduli):
+        P = _plain(n, q)
+        rows = []
+        for t in range(a.shape[1]):
+            bt = np.broadcast_to(b_hat[t, l], a[:, t, l].shape) if shared else b_hat[:, t, l]
+            rows.append(P.pointwise(P.forward(np.ascontiguousarray(a[:, t, l]), dtype=dt),
+                                    np.ascontiguousarray(bt), dtype=dt).astype(np.uint64))
+        out.append(P.inverse(_sum_mod(rows, q), dtype=dt).astype(np.uint64))
+    return np.stack(out, axis=1)
+
+
+@pytest.mark.parametrize("n", R.RANGE_N)
+@pytest.mark.parametrize("cls", list(CLASSES))
+def test_worst_case_ranges(n, cls, torch_cuda):
+    """Every word q_l - 1: the product against the oracle, and a seven-term mac (the largest
+    values the accumulator can hold in each class) against plain contexts' forward / pointwise /
+    inverse with the sum on the host, shared and per-batch."""
+    moduli = CLASSES[cls]
+    ctx = nttmul.RnsContext(n, moduli)
+    batch, terms, L = R.RANGE_BATCH, R.TERMS_LONG, len(moduli)
+    top = np.array([q - 1 for q in moduli], dtype=np.uint64)
+    a = np.ascontiguousarray(np.broadcast_to(top[None, None, :, None], (batch, terms, L, n)))
+    got, _ = _call(torch_cuda, ctx, "multiply", a[:, 0], a[:, 0])
+    want = np.stack([O.Plan(n, q).product_merged(a[0, 0, l], a[0, 0, l]) for l, q in enumerate(moduli)])
+    assert np.array_equal(got, np.broadcast_to(want, got.shape))
+    for shared in (False, True):
+        b_hat = a[0] if shared else a
+        got, _ = _call(torch_cuda, ctx, "mac", a, b_hat, shared=shared)
+        assert np.array_equal(got, _existing_mac(n, moduli, a, b_hat, shared, ctx.io_dtype)), shared
+    ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 5. rules of the device path
+# ---------------------------------------------------------------------------------------------
+
+def test_reversed_basis_permutes_the_limbs(torch_cuda):
+    """The same basis in reversed order gives the same limbs in reversed order, for every
+    operation: the table index and the addressing follow the limb, nothing else does."""
+    n, moduli = R.RULES
+    rev = moduli[::-1]
+    batch, terms = 5, 2
+    a, b = _operands(n, moduli, batch, terms, p0=70)
+    fwd_ctx, rev_ctx = nttmul.RnsContext(n, moduli), nttmul.RnsContext(n, rev)
+    b_hat = _plain_forward_terms(n, moduli, b, fwd_ctx.io_dtype)
+    flip = lambda x: np.ascontiguousarray(np.flip(x, axis=-2))          # noqa: E731
+    for op, x, y in (("multiply", a[:, 0], b[:, 0]), ("forward", a[:, 0], None),
+                     ("inverse", a[:, 0], None), ("mac", a, b_hat)):
+        got, _ = _call(torch_cuda, fwd_ctx, op, np.ascontiguousarray(x),
+                       None if y is None else np.ascontiguousarray(y))
+        got_rev, _ = _call(torch_cuda, rev_ctx, op, flip(x), None if y is None else flip(y))
+        assert np.array_equal(flip(got_rev), got), op
+    assert [rev_ctx.limb_info(l).q for l in range(3)] == list(rev)
+    info = fwd_ctx.limb_info(1)
+    assert (info.n, info.q, info.psi) == (n, moduli[1], nttmul.smallest_psi(n, moduli[1]))
+    fwd_ctx.close()
+    rev_ctx.close()
+
+
+def test_device_path_rules(torch_cuda):
+    """A non-default stream; the empty batch; bad arguments on a live context; shapes checked
+    before the call."""
+    torch = torch_cuda
+    n, moduli = R.RULES
+    ctx = nttmul.RnsContext(n, moduli)
+    batch, terms = 5, 2
+    a, b = _operands(n, moduli, batch, terms, p0=70)
+    side = torch.cuda.Stream()
+    want = np.stack([np.stack([O.Plan(n, q).product_merged(a[p, 0, l], b[p, 0, l])
+                               for l, q in enumerate(moduli)]) for p in range(batch)])
+    got, _ = _call(torch, ctx, "multiply", np.ascontiguousarray(a[:, 0]),
+                   np.ascontiguousarray(b[:, 0]), stream=side.cuda_stream)
+    assert np.array_equal(got, want)
+    b_hat = _plain_forward_terms(n, moduli, b, ctx.io_dtype)
+    shared, _ = _call(torch, ctx, "mac", a, np.ascontiguousarray(b_hat[0]), shared=True,
+                      stream=side.cuda_stream)
+    tiled = np.ascontiguousarray(np.broadcast_to(b_hat[0], a.shape))
+    per_batch, _ = _call(torch, ctx, "mac", a, tiled, stream=side.cuda_stream)
+    assert np.array_equal(shared, per_batch)
+    # an empty batch enqueues nothing and dereferences nothing
+    ctx.multiply_device(0, 0, 0, 0)
+    ctx.forward_device(0, 0, 0)
+    ctx.mac_ntt_device(0, 0, 0, 0, 1)
+    da = _to_dev(torch, a, 32)
+    for call in (lambda: ctx.mac_ntt_device(da, da, da, 1, 0),             # terms = 0
+                 lambda: ctx.mac_ntt_device(0, da, da, 1, 1),              # NULL c
+                 lambda: ctx.multiply_device(da, da, 0, 1),                # NULL b
+                 lambda: ctx.inverse_device(da, 0, 1)):                    # NULL in
+        with pytest.raises(nttmul.NttmulError) as ei:
+            call()
+        assert ei.value.status == nttmul.NTTMUL_EINVAL
+    with pytest.raises(nttmul.NttmulError) as ei:
+        p = da.data_ptr()
+        ctx.multiply_device(p, p, p, 1, dev=7)                             # not the context's
+    assert ei.value.status == nttmul.NTTMUL_ENODEV
+    with pytest.raises(ValueError):                                        # too few words
+        ctx.multiply_device(da, da, da, batch * terms + 1)
+    with pytest.raises(ValueError):                                        # 64-bit tensor
+        ctx.forward_device(da.to(torch.int64), da.to(torch.int64), 1)
+    with pytest.raises(nttmul.NttmulError) as ei:
+        ctx.kernel_name(4)
+    assert ei.value.status == nttmul.NTTMUL_EINVAL
+    ctx.close()
+    with pytest.raises(nttmul.NttmulError) as ei:
+        nttmul.RnsContext(R.UNSUPPORTED_N, moduli)
+    assert ei.value.status == nttmul.NTTMUL_EUNSUPPORTED
+
+
+@pytest.mark.parametrize("n,moduli,limb,other", R.VALIDATE)
+def test_validate_flag_checks_each_word_against_its_own_limb(n, moduli, limb, other, torch_cuda):
+    """NTTMUL_FLAG_VALIDATE: a word equal to q_limb in limb `limb` is NTTMUL_ERANGE in every
+    operand of every operation, while the same value in a limb with a larger modulus passes --
+    the check is per limb.  Clean operands pass, a shared b_hat too."""
+    torch = torch_cuda
+    ctx = nttmul.RnsContext(n, moduli, validate=True)
+    batch, terms = 3, 2
+    a, b = _operands(n, moduli, batch, terms, p0=80)
+    b_hat = _plain_forward_terms(n, moduli, b, ctx.io_dtype)
+    value = moduli[limb]
+    assert value < moduli[other]
+    calls = {"multiply": (a[:, 0], b[:, 0]), "forward": (a[:, 0], None),
+             "inverse": (a[:, 0], None), "mac": (a, b_hat)}
+    for op, (x, y) in calls.items():
+        x = np.ascontiguousarray(x)
+        y = None if y is None else np.ascontiguousarray(y)
+        _call(torch, ctx, op, x, y)                                         # clean
+        for which in (0, 1) if y is not None else (0,):
+            ops = [x.copy(), None if y is None else y.copy()]
+            ops[which][batch - 1, ..., other, n - 1] = value                # in range there
+            _call(torch, ctx, op, *ops)
+            ops[which][batch - 1, ..., limb, n - 1] = value                 # out of range here
+            with pytest.raises(nttmul.NttmulError) as ei:
+                _call(torch, ctx, op, *ops)
+            assert ei.value.status == nttmul.NTTMUL_ERANGE, (op, which)
+    y = np.ascontiguousarray(b_hat[0])
+    _call(torch, ctx, "mac", a, y, shared=True)
+    y[terms - 1, limb, n - 1] = value
+    with pytest.raises(nttmul.NttmulError) as ei:
+        _call(torch, ctx, "mac", a, y, shared=True)
+    assert ei.value.status == nttmul.NTTMUL_ERANGE
+    ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 6. host forms
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n,moduli", R.HOST)
+def test_host_forms(n, moduli, torch_cuda):
+    """nttmul_rns_multiply / forward / inverse / mac_ntt on numpy arrays; shapes are checked."""
+    ctx = nttmul.RnsContext(n, moduli)
+    dt = ctx.io_dtype
+    batch, terms = R.HOST_BATCH, R.HOST_TERMS
+    a, b = _operands(n, moduli, R.BATCH, _tmax(n))
+    a, b = np.ascontiguousarray(a[:batch, :terms]), np.ascontiguousarray(b[:batch, :terms])
+    got = ctx.multiply(a[:, 0], b[:, 0])
+    assert got.dtype == dt and got.shape == (batch, len(moduli), n)
+    want = np.stack([_oracle_products(n, q)[0][:batch, 0] for q in moduli], axis=1)
+    assert np.array_equal(got.astype(np.uint64), want)
+    hat = ctx.forward(a[:, 0])
+    assert np.array_equal(hat.astype(np.uint64), _plain_per_limb("forward", n, moduli, a[:, 0], dt))
+    assert np.array_equal(ctx.inverse(hat).astype(np.uint64), a[:, 0])
+    b_hat = np.stack([ctx.forward(b[:, t]) for t in range(terms)], axis=1)
+    for shared in (False, True):
+        got = ctx.mac_ntt(a, b_hat[0] if shared else b_hat, shared=shared)
+        assert got.dtype == dt and got.shape == (batch, len(moduli), n)
+        assert np.array_equal(got.astype(np.uint64), _expected_mac(n, moduli, terms, shared)[:batch])
+    with pytest.raises(ValueError):
+        ctx.mac_ntt(a, b_hat[0])                        # [terms, limbs, n] without shared
+    with pytest.raises(ValueError):
+        ctx.mac_ntt(a[:, 0], b_hat[:, 0])               # no terms axis
+    with pytest.raises(ValueError):
+        ctx.multiply(a[:, 0, :2], b[:, 0, :2])          # too few limbs
+    with pytest.raises(ValueError):
+        ctx.forward(a[0, 0])                            # no batch axis
+    ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 7. dispatch anchor
+# ---------------------------------------------------------------------------------------------
+
+def test_mirror_agrees_with_the_library_dispatch(torch_cuda):
+    """nttmul_rns_kernel_name (the dry run of the launching statement) equals the mirror's kernel
+    for every case of tests/rns_cases.py, and names a kernel of the loaded code object."""
+    table = nttmul.kernel_hashes(nttmul.RNS_LIB_PATH)
+    ctxs = {}
+    for case in R.all_cases():
+        ck = (case.n, case.moduli)
+        if ck not in ctxs:
+            ctxs[ck] = nttmul.RnsContext(case.n, case.moduli)
+        name = ctxs[ck].kernel_name(case.op)
+        assert name == R.rns_kernel(case.op, case.n, case.moduli), case
+        assert name in table, name
+        assert ctxs[ck].kernel_name(R.OPS.index(case.op)) == name
+    assert len(ctxs) >= 20
+    for ctx in ctxs.values():
+        ctx.close()
