@@ -231,6 +231,35 @@ SERVER_SHAPES = [(512, 1), (512, 2), (1024, 1), (256, 2), (256, 3), (256, 4)]
 SERVER_BITS = (14, 17, 20, 24, 28, 30, 31)
 SERVER_NAMED = (Q0, Q31, Q31HI, Q31LO)
 
+# 4. inputs that saturate a stage boundary (tests/test_gpu_saturation.py, tests/saturation.py)
+SAT_N = (256, 1024, 4096, 8192, 65536)
+# nttmul.find_prime(n, 31): the largest prime below 2^31 with 2n | q - 1
+SAT_P31 = {256: 2147483137, 1024: 2147473409, 4096: 2147377153, 8192: Q31HI, 65536: Q31HI}
+SAT_U64_N = (4096, 8192)        # 64-bit words on the 32-bit moduli
+SAT_SERVER = (256, Q31HI)       # the same family call by call through the resident server
+SAT_MAC_N = (256, 4096)
+SAT_MAC_TERMS = 7
+
+
+def sat_moduli(n):
+    out = []
+    for q in (Q31HI, SAT_P31[n], Q32, Q62):
+        if q not in out:
+            out.append(q)
+    return out
+
+
+def sat_products():
+    """(n, q, word_bits): one launch each."""
+    return [(n, q, w) for n in SAT_N for q in sat_moduli(n)
+            for w in ((native_bits(q),) + ((64,) if q < (1 << 32) and n in SAT_U64_N else ()))]
+
+
+def sat_batch(n):
+    """Polynomials per launch: two value pairs and one random partner per m = 1, 2, ..., n."""
+    return 3 * n.bit_length()
+
+
 # ---------------------------------------------------------------------------------------------
 # Case tables: the parametrisations of tests/test_gpu_parity.py
 # ---------------------------------------------------------------------------------------------
@@ -305,6 +334,13 @@ def new_cases():
     out.append(Case("multiply", n, q, w, batch))
     for n, batch in SERVER_SHAPES:
         out += [Case("multiply", n, q, 32, batch, path="server") for q in SERVER_NAMED]
+    out += [Case("multiply", n, q, w, sat_batch(n)) for n, q, w in sat_products()]
+    for n in SAT_N:
+        for q in sat_moduli(n):
+            w = native_bits(q)
+            out += [Case("transform", n, q, w, n.bit_length(), mode=0),
+                    Case("transform", n, q, w, n.bit_length(), mode=3)]
+    out.append(Case("multiply", SAT_SERVER[0], SAT_SERVER[1], 32, 1, path="server"))
     return out
 
 

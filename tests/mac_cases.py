@@ -56,6 +56,9 @@ def all_cases():
     out = parity_cases()
     out += [Case(n, q, D.native_bits(q), TERMS_LONG, s, RANGE_BATCH)
             for n in RANGE_N for q in RANGE_MODULI if q for s in (False, True)]
+    # saturated operands (tests/test_gpu_saturation.py): S(1, q - 1) against b_hat = q - 1
+    out += [Case(n, q, D.native_bits(q), D.SAT_MAC_TERMS, s, RANGE_BATCH)
+            for n in D.SAT_MAC_N for q in D.sat_moduli(n) for s in (False, True)]
     n, q, w = RULES
     out += [Case(n, q, w, 2, s, 5) for s in (False, True)]
     n, q, w = VALIDATE
