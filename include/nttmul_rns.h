@@ -48,7 +48,8 @@
  * Out of scope here:
  *   - n > 4096 (the column passes of the multi-pass product are not limb-aware);
  *   - 64-bit storage of 32-bit limbs, and the class 2^31 <= q < 2^32;
- *   - base conversion and CRT reconstruction between bases;
+ *   - CRT reconstruction (base conversion between bases: include/nttmul_bconv.h,
+ *     lib/libnttmul_bconv.so);
  *   - a chunked or multi-device host path (the host forms below are deliberately simple);
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC).
  */

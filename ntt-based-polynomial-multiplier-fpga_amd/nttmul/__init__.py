@@ -736,7 +736,11 @@ def load_rns_library() -> ctypes.CDLL:
         return _RNS_LIB
     if not os.path.exists(RNS_LIB_PATH):
         raise ImportError(f"{RNS_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
-    lib = _bind_mac(_bind(ctypes.CDLL(RNS_LIB_PATH)))
+    _RNS_LIB = _bind_rns(_bind_mac(_bind(ctypes.CDLL(RNS_LIB_PATH))))
+    return _RNS_LIB
+
+
+def _bind_rns(lib: ctypes.CDLL) -> ctypes.CDLL:
     vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
     lib.nttmul_rns_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(_Params), sz,
                                       ctypes.POINTER(ctypes.c_uint64), u32]
@@ -755,7 +759,6 @@ def load_rns_library() -> ctypes.CDLL:
     lib.nttmul_rns_inverse.argtypes = [vp, vp, vp, sz]
     lib.nttmul_rns_mac_ntt.argtypes = [vp, vp, vp, vp, sz, u32, i32]
     lib.nttmul_rns_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
-    _RNS_LIB = lib
     return lib
 
 
@@ -911,6 +914,179 @@ class RnsContext:
                                                  b_hat.ctypes.data, a.shape[0], a.shape[1],
                                                  int(shared)))
         return c
+
+
+# ---- RNS base conversion and ModDown (include/nttmul_bconv.h) ------------------------------------
+
+BCONV_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_bconv.so")
+BCONV_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_bconv.h")
+BCONV_OPS = ("convert", "moddown")                    # nttmul_bconv_kernel_name's op numbers
+
+_BCONV_LIB: Optional[ctypes.CDLL] = None
+
+
+class BconvInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("from_limbs", ctypes.c_uint32),
+                ("to_limbs", ctypes.c_uint32), ("word_bits", ctypes.c_uint32),
+                ("ndev", ctypes.c_int)]
+
+
+def load_bconv_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_bconv.so (include/nttmul_bconv.h): the ABI and kernels of
+    libnttmul_rns.so plus the base-conversion kernels.  The other loaders are unaffected."""
+    global _BCONV_LIB
+    if _BCONV_LIB is not None:
+        return _BCONV_LIB
+    if not os.path.exists(BCONV_LIB_PATH):
+        raise ImportError(f"{BCONV_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
+    lib = _bind_rns(_bind_mac(_bind(ctypes.CDLL(BCONV_LIB_PATH))))
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u64p, prm = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_Params)
+    lib.nttmul_bconv_create.argtypes = [ctypes.POINTER(vp), prm, sz, u64p, u32, u64p, u32]
+    lib.nttmul_bconv_destroy.argtypes = [vp]
+    lib.nttmul_bconv_destroy.restype = None
+    lib.nttmul_bconv_last_error.argtypes = [vp]
+    lib.nttmul_bconv_last_error.restype = ctypes.c_char_p
+    lib.nttmul_bconv_get_info.argtypes = [vp, ctypes.POINTER(BconvInfo)]
+    lib.nttmul_bconv_plan.argtypes = [prm, sz, u64p, u32, u64p, u32, u64p, u64p, u64p]
+    for op in BCONV_OPS:
+        getattr(lib, f"nttmul_bconv_{op}_device").argtypes = [vp, vp, vp, sz, i32, vp]
+        getattr(lib, f"nttmul_bconv_{op}").argtypes = [vp, vp, vp, sz]
+    lib.nttmul_bconv_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
+    _BCONV_LIB = lib
+    return lib
+
+
+def bconv_exported_symbols() -> list:
+    """Function names declared in include/nttmul_bconv.h."""
+    import re
+    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_bconv_\w+)\s*\(",
+                                 open(BCONV_HEADER_PATH).read(), re.M)))
+
+
+def _bconv_bases(n, from_q, to_q, flags):
+    from_q, to_q = [int(q) for q in from_q], [int(q) for q in to_q]
+    prm = _Params(n, 0, 0, 1, 0, flags, 0, 0, 0, 0, 0)
+    fq = (ctypes.c_uint64 * max(1, len(from_q)))(*from_q)
+    tq = (ctypes.c_uint64 * max(1, len(to_q)))(*to_q)
+    return from_q, to_q, prm, fq, tq
+
+
+def bconv_plan(n: int, from_q, to_q, flags: int = 0):
+    """nttmul_bconv_plan, without a device: (inv, w, binv) as lists of Python integers with
+    inv[i] = Bh_i^-1 mod b_i, w[i][j] = Bh_i mod c_j, binv[j] = B^-1 mod c_j.  Raises NttmulError
+    with the status nttmul_bconv_create would return for these bases."""
+    lib = load_bconv_library()
+    from_q, to_q, prm, fq, tq = _bconv_bases(n, from_q, to_q, flags)
+    L, K = len(from_q), len(to_q)
+    inv, w, binv = ((ctypes.c_uint64 * max(1, k))() for k in (L, L * K, K))
+    st = lib.nttmul_bconv_plan(ctypes.byref(prm), ctypes.sizeof(prm), fq, L, tq, K, inv, w, binv)
+    if st != NTTMUL_OK:
+        raise NttmulError(st, lib.nttmul_strerror(st).decode())
+    return list(inv[:L]), [list(w[i * K:(i + 1) * K]) for i in range(L)], list(binv[:K])
+
+
+class BaseConverter:
+    """nttmul_bconv: conversion from the basis from_q (L primes) to the disjoint basis to_q
+    (K primes) of one word class for one degree n <= 4096 (include/nttmul_bconv.h).  convert maps
+    [batch, L, n] to [batch, K, n]; moddown maps [batch, K + L, n] (limbs of to_q, then of from_q)
+    to [batch, K, n].  Words are word_bits wide."""
+
+    def __init__(self, n: int, from_q, to_q, ndev: int = 1, first_dev: int = 0,
+                 validate: bool = False, cyclic: bool = False, share_devices: bool = False):
+        self._lib = load_bconv_library()
+        self._h = ctypes.c_void_p()
+        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
+                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
+        from_q, to_q, prm, fq, tq = _bconv_bases(n, from_q, to_q, flags)
+        prm.ndev, prm.first_dev = ndev, first_dev
+        st = self._lib.nttmul_bconv_create(ctypes.byref(self._h), ctypes.byref(prm),
+                                           ctypes.sizeof(prm), fq, len(from_q), tq, len(to_q))
+        if st != NTTMUL_OK:
+            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
+        info = BconvInfo()
+        self._lib.nttmul_bconv_get_info(self._h, ctypes.byref(info))
+        self.info = info
+        self.n, self.word_bits = info.n, info.word_bits
+        self.from_limbs, self.to_limbs = info.from_limbs, info.to_limbs
+        self.from_q, self.to_q = tuple(from_q), tuple(to_q)
+        self.first_dev = first_dev
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.nttmul_bconv_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, st: int):
+        if st != NTTMUL_OK:
+            raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
+                                  f"{self._lib.nttmul_bconv_last_error(self._h).decode()}")
+
+    @property
+    def io_dtype(self):
+        return np.uint32 if self.word_bits == 32 else np.uint64
+
+    def kernel_name(self, op) -> str:
+        """nttmul_bconv_kernel_name for op 0..1 or "convert" / "moddown", e.g. "k_bconv<u32,0>"."""
+        op = BCONV_OPS.index(op) if isinstance(op, str) else int(op)
+        buf = ctypes.create_string_buffer(256)
+        st = self._lib.nttmul_bconv_kernel_name(self._h, op, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def _in_limbs(self, op: str) -> int:
+        return self.from_limbs + (self.to_limbs if op == "moddown" else 0)
+
+    # device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`
+
+    def _device(self, op, out, x, batch, dev, stream):
+        dev = self.first_dev if dev is None else dev
+        args = [_dev_arg(t, batch * k, self.n, self.word_bits, dev)
+                for t, k in ((out, self.to_limbs), (x, self._in_limbs(op)))]
+        fn = getattr(self._lib, f"nttmul_bconv_{op}_device")
+        self._check(fn(self._h, *args, batch, dev, stream or None))
+
+    def convert_device(self, out, x, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """x [batch][from_limbs][n] -> out [batch][to_limbs][n]."""
+        self._device("convert", out, x, batch, dev, stream)
+
+    def moddown_device(self, out, x, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """x [batch][to_limbs + from_limbs][n] -> out [batch][to_limbs][n]."""
+        self._device("moddown", out, x, batch, dev, stream)
+
+    # host arrays
+
+    def _host(self, op, x):
+        x = np.ascontiguousarray(x, dtype=self.io_dtype)
+        if x.ndim != 3 or x.shape[1:] != (self._in_limbs(op), self.n):
+            raise ValueError(f"{op}: x must have shape [batch, {self._in_limbs(op)}, {self.n}]")
+        out = np.empty((x.shape[0], self.to_limbs, self.n), dtype=self.io_dtype)
+        fn = getattr(self._lib, f"nttmul_bconv_{op}")
+        self._check(fn(self._h, out.ctypes.data, x.ctypes.data, x.shape[0]))
+        return out
+
+    def convert(self, x) -> np.ndarray:
+        """out[p][j] = (sum_i (x[p][i] Bh_i^-1 mod b_i) Bh_i) mod c_j for x of shape
+        [batch, from_limbs, n]; returns [batch, to_limbs, n]."""
+        return self._host("convert", x)
+
+    def moddown(self, x) -> np.ndarray:
+        """out[p][j] = (x[p][j] - convert(x[p][to_limbs:])[j]) B^-1 mod c_j for x of shape
+        [batch, to_limbs + from_limbs, n]; returns [batch, to_limbs, n]."""
+        return self._host("moddown", x)
 
 
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
