@@ -26,6 +26,15 @@
  * checks them on the device and returns NTTMUL_ERANGE.  New-API inputs are const (never clobbered).
  * A context is used by one host thread at a time; separate contexts are independent.  There is no
  * CPU fallback: without a usable HIP device nttmul_create fails with NTTMUL_ENODEV.
+ *
+ * Caller memory (host and device buffers alike; tests/test_gpu_footprint.py):
+ *   Alignment.  Operands need the alignment of their word only (4 bytes for 32-bit words, 8 for
+ *     64-bit words): every kernel touches caller memory one word per lane.
+ *   Aliasing.  out == in is allowed for every transform (nttmul_forward_*, nttmul_inverse_*,
+ *     nttmul_transform_* in every mode), and c == a or c == b for nttmul_pointwise_*.  For
+ *     products c must not overlap a or b.  Partial overlap of two operands is never allowed.
+ *   Footprint.  A call writes exactly batch * n words of its output (of both outputs for
+ *     nttmul_fill_random_device) and nothing else in caller memory; inputs are never written.
  */
 #ifndef NTTMUL_H
 #define NTTMUL_H

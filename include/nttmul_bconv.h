@@ -41,6 +41,8 @@
  * no-op.  NTTMUL_ENODEV as in nttmul.h (no device, or `dev` not one of the converter's).
  *
  * Aliasing: out must not overlap the input.  Operands need the alignment of their word only.
+ * Footprint: a call writes exactly batch * to_limbs * n words of out and nothing else in caller
+ * memory; the input is never written (tests/test_gpu_footprint.py).
  *
  * NTTMUL_FLAG_VALIDATE range-checks every input word against its own limb's modulus on the device
  * and returns NTTMUL_ERANGE; the call then waits for the check.

@@ -21,6 +21,11 @@
  *          accepted, whether or not it is the transform of something.
  *   c      [batch][n], standard order, canonical.  c must not overlap a or b_hat.
  *
+ * Caller memory, as in nttmul.h (tests/test_gpu_footprint.py).  Alignment: operands need the
+ * alignment of their word only.  Aliasing: none is allowed here; c must not overlap a or b_hat,
+ * not even exactly.  Footprint: a call writes exactly batch * n words of c and nothing else in
+ * caller memory; a and b_hat are never written.
+ *
  * terms = 1 multiplies by an NTT-domain operand.  With b_hat = forward(b) the result equals, bit
  * for bit, the sum over t of nttmul_multiply(a[p][t], b[..][t]) mod q.
  *

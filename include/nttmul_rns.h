@@ -35,8 +35,12 @@
  * NTTMUL_FLAG_CYCLIC and for the word classes above.  batch = 0 is a successful no-op.
  * NTTMUL_ENODEV as in nttmul.h (no device, or `dev` not one of the context's).
  *
- * Aliasing: out == in is allowed for the two transforms (in place).  c must not overlap a, b or
- * b_hat.
+ * Caller memory, as in nttmul.h (tests/test_gpu_footprint.py).
+ *   Alignment.  Operands need the alignment of their word only.
+ *   Aliasing.  out == in is allowed for the two transforms (in place).  c must not overlap a, b
+ *     or b_hat.  Partial overlap of two operands is never allowed.
+ *   Footprint.  A call writes exactly batch * limbs * n words of its output and nothing else in
+ *     caller memory; inputs are never written.
  *
  * NTTMUL_FLAG_VALIDATE range-checks every operand word against its own limb's modulus on the
  * device (word i belongs to limb (i / n) mod limbs) and returns NTTMUL_ERANGE; the call then

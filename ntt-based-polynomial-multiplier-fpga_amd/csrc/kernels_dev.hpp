@@ -1124,9 +1124,11 @@ __global__ __launch_bounds__(LOGS == 8 ? 512 : LOGS == 9 ? 64 : 128) void k_serv
 // twice the independent butterflies per lane).
 template <class A, int L1, int DIR>
 constexpr int xform_upg() { return L1 == 0 && sizeof(typename A::word) == 4 ? 2 : 1; }
+// in == out is allowed (no __restrict__ on the two; include/nttmul.h "Aliasing"): a thread group
+// reads its polynomials whole before the first exchange barrier and writes them after the last.
 template <class A, class TIn, class TOut, int LOGS, int L1, int DIR>
-__global__ __launch_bounds__(256) void k_xform(KParams<A> P, const TIn *__restrict__ in,
-                                               TOut *__restrict__ out, size_t units) {
+__global__ __launch_bounds__(256) void k_xform(KParams<A> P, const TIn *in, TOut *out,
+                                               size_t units) {
   using W = typename A::word;
   using Gr = Groups<LOGS>;
   constexpr int N = Gr::N, TP = N / 16, PB = 256 / TP, G = Gr::G, NP = Gr::NP;
@@ -1188,9 +1190,9 @@ __global__ __launch_bounds__(256) void k_xform(KParams<A> P, const TIn *__restri
 
 // c = a * b mod q coefficient-wise (NTT/ntt.C:131-137 mul_array), canonical in and out:
 // two Montgomery products, the second by R^2 mod q (P.f holds R^2 mod q for this kernel).
+// c == a and c == b are allowed (no __restrict__): word i is read and written by one thread.
 template <class A, class IO>
-__global__ __launch_bounds__(256) void k_pointwise(KParams<A> P, const IO *__restrict__ a,
-                                                   const IO *__restrict__ b, IO *__restrict__ c,
+__global__ __launch_bounds__(256) void k_pointwise(KParams<A> P, const IO *a, const IO *b, IO *c,
                                                    size_t total) {
   using W = typename A::word;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

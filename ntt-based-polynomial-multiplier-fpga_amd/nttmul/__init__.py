@@ -444,7 +444,14 @@ def _dev_arg(x, batch: int, n: int, word_bits: int, dev: int) -> int:
 
 
 class Context:
-    """An (n, q) multiplier bound to one or more HIP devices (≙ an opened FPGA handle)."""
+    """An (n, q) multiplier bound to one or more HIP devices (≙ an opened FPGA handle).
+
+    Caller memory (include/nttmul.h; host arrays and device tensors alike).  Alignment: operands
+    need the alignment of their word only.  Aliasing: out may be the input itself for every
+    transform (forward, inverse, transform in every mode), and c may be a or b for pointwise; for
+    products c must not overlap a or b; partial overlap is never allowed.  Footprint: a call
+    writes exactly batch * n words of its output and nothing else in caller memory; inputs are
+    never written."""
 
     def __init__(self, n: int, q: int, psi: int = 0, ndev: int = 1, first_dev: int = 0,
                  validate: bool = False, cyclic: bool = False, share_devices: bool = False,
@@ -672,7 +679,11 @@ def mac_exported_symbols() -> list:
 
 class MacContext(Context):
     """A Context created through lib/libnttmul_mac.so: every Context method, plus
-    c[p] = INTT(sum_t NTT(a[p][t]) o b_hat[p or 0][t]) for n <= 4096 (include/nttmul_mac.h)."""
+    c[p] = INTT(sum_t NTT(a[p][t]) o b_hat[p or 0][t]) for n <= 4096 (include/nttmul_mac.h).
+
+    Caller memory, as for Context: operands need the alignment of their word only; c must not
+    overlap a or b_hat (no aliasing form is allowed); a call writes exactly batch * n words of c
+    and nothing else in caller memory, and never writes a or b_hat."""
 
     def __init__(self, n: int, q: int, **kw):
         super().__init__(n, q, _lib=load_mac_library(), **kw)
@@ -772,7 +783,12 @@ def rns_exported_symbols() -> list:
 class RnsContext:
     """nttmul_rns: the moduli q_0 .. q_{L-1} of one degree n <= 4096, every operation one launch
     over [batch, limbs, n] operands (include/nttmul_rns.h).  Words are info.word_bits wide: 32
-    when every q_l < 2^31, 64 when every q_l >= 2^32."""
+    when every q_l < 2^31, 64 when every q_l >= 2^32.
+
+    Caller memory, as for Context: operands need the alignment of their word only; out may be the
+    input itself for forward and inverse, c must not overlap a, b or b_hat, and partial overlap is
+    never allowed; a call writes exactly batch * limbs * n words of its output and nothing else
+    in caller memory, and never writes an input."""
 
     def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
                  cyclic: bool = False, share_devices: bool = False):

@@ -57,7 +57,46 @@ def all_cases():
             out.append(Case(op, bits, N, BATCH, *HOST[bits]))
         out += [Case("moddown", bits, N, BATCH, L, 3) for L in EXACT_L]
     out += [Case(op, 32, N, BATCH, 2, 1) for op in OPS] + [Case(op, 32, N, BATCH, 1, 2) for op in OPS]
+    out += [f.case for f in footprint_cases()]
     return out
+
+
+# The caller's memory (tests/test_gpu_footprint.py).  n = 256 with batch 1 and 5: on 32-bit words
+# a workgroup takes four 256-word slices, so both batches end in a partial workgroup (5 = 4 + 1);
+# on 64-bit words a workgroup takes one slice, so those cases have no partial workgroup and
+# exercise guards and alignment only.  n = 4096 with batch 1.  (L, K) = (3, 2) and (1, 5): K = 5
+# leaves a padded target-limb tile, whose jx clamp reads limb K - 1 (csrc/bconv_dev.hpp:152).
+# host: "" for a *_device call, "host" for the host form.
+Footprint = namedtuple("Footprint", "entry case host", defaults=("",))
+FP_SHAPES = ((3, 2), (1, 5))
+FP_SIZES = ((256, 1), (256, 5), (4096, 1))           # (n, batch)
+FP_HOST_SIZE = (256, 5)
+
+
+def footprint_cases():
+    out = []
+    for bits in (32, 64):
+        for op in OPS:
+            for L, K in FP_SHAPES:
+                out += [Footprint(f"nttmul_bconv_{op}_device", Case(op, bits, n, batch, L, K))
+                        for n, batch in FP_SIZES]
+                out.append(Footprint(f"nttmul_bconv_{op}", Case(op, bits, *FP_HOST_SIZE, L, K), "host"))
+    return out
+
+
+def units_per_block(case):
+    """{kernel_key: (slices per workgroup, slices of the launch, 256)}: a slice is 256 consecutive
+    coefficients of one polynomial, a workgroup takes BconvArith<W>::kV = 4 (32-bit words) or 1
+    (64-bit words) of them (csrc/bconv_dev.hpp:60, :86, `live[v]` :138; csrc/bconv.hip:11)."""
+    return {bconv_kernel(case.op, case.n, case.bits): (4 if case.bits == 32 else 1,
+                                                       case.batch * (case.n // 256), 256)}
+
+
+def fp_guard_words(case):
+    """The guard width tests/guarded.py gives the call: the widest batch entry is moddown's input,
+    (K + L) * n words."""
+    from guarded import guard_words
+    return guard_words((case.K + case.L) * case.n)
 
 
 # ---------------------------------------------------------------------------------------------

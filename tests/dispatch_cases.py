@@ -261,6 +261,182 @@ def sat_batch(n):
 
 
 # ---------------------------------------------------------------------------------------------
+# Case tables: the caller's memory (tests/test_gpu_footprint.py, tests/guarded.py)
+# ---------------------------------------------------------------------------------------------
+
+# A footprint case: the exported entry point it calls, the launch it makes (a Case row, so the
+# kernel ledger sees it), and how it is called.  alias: "" (distinct buffers), "out=in" (a
+# transform in place), "c=a" / "c=b" (a pointwise product over an operand).  host: "" for a
+# *_device call, else the host path the call must report through nttmul_last_host_path:
+# "staged" (0), "direct" (1), "zero_copy" (2), "server" (3).
+Footprint = namedtuple("Footprint", "entry case cyclic scratch_mb alias host",
+                       defaults=(False, 0, "", ""))
+
+FP_N = (256, 512, 1024, 2048, 4096, 8192, 65536)
+FP_CYCLIC_N = (256, 4096, 65536)
+FP_INPLACE_N = (256, 4096, 8192, 65536)
+FP_INPLACE_BATCH = 3
+# the sub-batched path (scratch_mb = 1), shapes of SUBBATCH: sub-batches of 32 + 32 + 1 and
+# 2 + 2 + 1 polynomials; one product and the two reordered transform modes
+FP_SUBBATCH = [(8192, Q31, 32, 65), (65536, Q62, 64, 5)]
+FP_SUBBATCH_MODES = (2, 1)
+# NTTMUL_FLAG_VALIDATE, one case per arithmetic class (k_check_range<u32> and <u64>): the call
+# returns OK, so the range check read no guard word (every guard word is >= q)
+FP_VALIDATE = [(512, Q31HI, 32), (2048, Q32, 64), (256, Q62, 64)]
+# Host-buffer calls.  Staged copies go through CopyPool::copy (csrc/copy_pool.hpp), which splits
+# a copy of at least 2 MiB (parts = min(threads, bytes / 1 MiB) > 1) into pieces of
+# ceil(bytes / parts) rounded up to 4 KiB.  At n = 4096 in 32-bit words (16 KiB per polynomial)
+# two pieces are always equal (batch * 8 KiB is whole pages); the smallest batch with unequal
+# pieces is 193: 3,162,112 bytes, three parts, pieces of 1,056,768 + 1,056,768 + 1,048,576 bytes.
+FP_STAGED_SPLIT = (4096, Q31, 32, 193)
+FP_HOST_BATCH = 3
+FP_HOST_SHAPES = {
+    # path: (n, q, word_bits) for multiply, forward, inverse, pointwise and transform
+    "staged": [(1024, Q32, 64), (8192, Q62, 64)],
+    "direct": [(4096, Q31, 32), (8192, Q62, 64)],
+    # chunks of at most 64 KiB per operand (the default zero_copy_kb) at n <= 4096; a non-Plantard
+    # modulus, so the small products are not the resident server's
+    "zero_copy": [(1024, Q32, 32), (512, Q62, 64)],
+}
+FP_SERVER = [(256, Q31HI, 1), (256, Q31HI, 3)]
+
+
+def fp_batches(n):
+    """1 and 33 up to n = 4096: 33 leaves exactly one live unit in the last block for every
+    units-per-block value of the code (2, 4, 8, 16, 32) and a half-empty last pair of the
+    two-polynomial transforms.  1 and 3 above (3 x 65536 x 8 B = 1.5 MiB per operand)."""
+    return (1, 33) if n <= 4096 else (1, 3)
+
+
+def fp_device_shapes():
+    """(n, q, cyclic): every size and class negacyclic, three sizes cyclic."""
+    return ([(n, q, False) for n in FP_N for q in CLASS_MODULI]
+            + [(n, q, True) for n in FP_CYCLIC_N for q in CLASS_MODULI])
+
+
+def footprint_cases():
+    out = []
+    F = Footprint
+
+    def xf(n, q, w, batch, mode, **kw):
+        return Case("transform", n, q, w, batch, mode=mode, **kw)
+
+    for n, q, cyclic in fp_device_shapes():
+        for w in word_options(q):
+            for batch in fp_batches(n):
+                out += [F("nttmul_fill_random_device", Case("fill", n, q, w, batch), cyclic),
+                        F("nttmul_multiply_batch_device", Case("multiply", n, q, w, batch), cyclic),
+                        F("nttmul_forward_batch_device", xf(n, q, w, batch, 0), cyclic),
+                        F("nttmul_inverse_batch_device", xf(n, q, w, batch, 3), cyclic),
+                        F("nttmul_pointwise_batch_device", Case("pointwise", n, q, w, batch), cyclic)]
+                out += [F("nttmul_transform_device", xf(n, q, w, batch, m), cyclic) for m in XF_MODES]
+    for n, q, w, batch in FP_SUBBATCH:
+        out.append(F("nttmul_multiply_batch_device", Case("multiply", n, q, w, batch), scratch_mb=1))
+        out += [F("nttmul_transform_device", xf(n, q, w, batch, m), scratch_mb=1)
+                for m in FP_SUBBATCH_MODES]
+    for n, q, w in FP_VALIDATE:
+        b = fp_batches(n)[1]
+        out += [F("nttmul_multiply_batch_device", Case("multiply", n, q, w, b, validate=True)),
+                F("nttmul_forward_batch_device", xf(n, q, w, b, 0, validate=True)),
+                F("nttmul_pointwise_batch_device", Case("pointwise", n, q, w, b, validate=True))]
+    # in place
+    b = FP_INPLACE_BATCH
+    for n in FP_INPLACE_N:
+        for q in CLASS_MODULI:
+            for cyclic in (False, True):
+                for w in word_options(q):
+                    out += [F("nttmul_transform_device", xf(n, q, w, b, m), cyclic, alias="out=in")
+                            for m in XF_MODES]
+                    out += [F("nttmul_pointwise_batch_device", Case("pointwise", n, q, w, b), cyclic,
+                              alias=al) for al in ("c=a", "c=b")]
+    for n, q, w, batch in FP_SUBBATCH:
+        out += [F("nttmul_transform_device", xf(n, q, w, batch, m), scratch_mb=1, alias="out=in")
+                for m in XF_MODES]
+    # host buffers
+    n, q, w, batch = FP_STAGED_SPLIT
+    out.append(F(f"nttmul_multiply_batch_u{w}", Case("multiply", n, q, w, batch), host="staged"))
+    b = FP_HOST_BATCH
+    for path, shapes in FP_HOST_SHAPES.items():
+        for n, q, w in shapes:
+            out += [F(f"nttmul_multiply_batch_u{w}", Case("multiply", n, q, w, b), host=path),
+                    F(f"nttmul_forward_batch_u{w}", xf(n, q, w, b, 0), host=path),
+                    F(f"nttmul_inverse_batch_u{w}", xf(n, q, w, b, 3), host=path),
+                    F(f"nttmul_pointwise_batch_u{w}", Case("pointwise", n, q, w, b), host=path),
+                    F(f"nttmul_transform_batch_u{w}", xf(n, q, w, b, 2), host=path),
+                    # and in place, as the ntt256 shims call them
+                    F(f"nttmul_transform_batch_u{w}", xf(n, q, w, b, 1), host=path, alias="out=in"),
+                    F(f"nttmul_pointwise_batch_u{w}", Case("pointwise", n, q, w, b), host=path,
+                      alias="c=a")]
+    for n, q, batch in FP_SERVER:
+        out.append(F("nttmul_multiply_batch_u32", Case("multiply", n, q, 32, batch, path="server"),
+                     host="server"))
+    # the one-polynomial entry points: the server on 32-bit words, zero-copy on 64-bit words
+    out.append(F("nttmul_multiply_u32", Case("multiply", 256, Q31HI, 32, 1, path="server"),
+                 host="server"))
+    out.append(F("nttmul_multiply_u64", Case("multiply", 256, Q62, 64, 1), host="zero_copy"))
+    return out
+
+
+def units_per_block(case, cus=MI355X_CUS):
+    """{kernel_key: (units per workgroup, units of the launch, words per unit)} for the kernels
+    `case` launches.
+    A unit is what one thread group of the kernel owns and what its end-of-batch predicate counts:
+
+    * k_rows: rows of 2^LOGS words, PB = rows_threads(LOGS) / (2^LOGS / 16) per workgroup with
+      rows_threads(10) = 64, else 256 (csrc/kernels_dev.hpp:545, :591, `live` :600); a multi-pass
+      row pass runs batch * 2^L1 rows;
+    * k_xform: 256 / (2^LOGS / 16) thread groups of xform_upg = 2 polynomials on 32-bit
+      arithmetic with L1 == 0, else 1 (kernels_dev.hpp:1126, :1134, `live` / `live2` :1141;
+      csrc/kernels.hip:151 sizes the grid with the same product);
+    * k_cols8: one workgroup per 16 columns, the grid is exact (kernels_dev.hpp:1307);
+    * k_cols_fwd / k_cols_inv: one column per thread, 256 per workgroup, 2^LOGS columns per
+      polynomial (kernels_dev.hpp:1216, :1254; kernels.hip:44, :173);
+    * k_pointwise, k_fill, k_bitrev, k_bitrev_inplace, k_check_range: one word per thread, 256 per
+      workgroup (kernels_dev.hpp:1199, :1395, :1409, :1416, :1429);
+    * k_server: one resident workgroup, results leave through the library's own mailbox and a
+      host memcpy of batch * n words (csrc/nttmul.cpp:686)."""
+    import re
+    out = {}
+    for key in kernels_of(case, cus):
+        name, args = re.fullmatch(r"(\w+)<(.*)>", key).groups()
+        args = args.split(",")
+        if name == "k_rows":
+            logs, l1 = int(args[3]), int(args[4])
+            out[key] = ((64 if logs == 10 else 256) // ((1 << logs) // 16), case.batch << l1, 1 << logs)
+        elif name == "k_xform":
+            logs, l1 = int(args[3]), int(args[4])
+            upg = 2 if l1 == 0 and args[0] != "Arith64" else 1
+            out[key] = (256 // ((1 << logs) // 16) * upg, case.batch << l1, 1 << logs)
+        elif name == "k_cols8":
+            out[key] = (1, case.batch * 16, 4096)
+        elif name in ("k_cols_fwd", "k_cols_inv"):
+            out[key] = (256, case.batch * (case.n >> int(args[2])), 1)
+        elif name == "k_server":
+            out[key] = (1, case.batch, case.n)
+        else:
+            assert name in ("k_pointwise", "k_fill", "k_bitrev", "k_bitrev_inplace",
+                            "k_check_range"), key
+            out[key] = (256, case.batch * case.n, 1)
+    return out
+
+
+# Kernels whose launches never end in a partial workgroup, whatever the batch: (regular expression
+# over the kernel_key, reason).  Every other multi-unit kernel needs a footprint case with one.
+FP_ALWAYS_WHOLE = (
+    (r"k_(pointwise|fill|bitrev|bitrev_inplace|check_range)<.*>|k_cols_(fwd|inv)<.*>",
+     "one word or column per thread: batch * n and batch * 2^LOGS are multiples of 256"),
+    (r"k_(rows|xform)<\w+,u\d+,u\d+,8,8,\w+>",
+     "the square split's row pass runs batch * 256 rows, 16 per workgroup"),
+)
+
+
+def fp_guard_words(case):
+    """The guard width tests/guarded.py gives a libnttmul call: one batch entry is n words."""
+    from guarded import guard_words
+    return guard_words(case.n)
+
+
+# ---------------------------------------------------------------------------------------------
 # Case tables: the parametrisations of tests/test_gpu_parity.py
 # ---------------------------------------------------------------------------------------------
 
@@ -341,6 +517,7 @@ def new_cases():
             out += [Case("transform", n, q, w, n.bit_length(), mode=0),
                     Case("transform", n, q, w, n.bit_length(), mode=3)]
     out.append(Case("multiply", SAT_SERVER[0], SAT_SERVER[1], 32, 1, path="server"))
+    out += [f.case for f in footprint_cases()]
     return out
 
 

@@ -65,7 +65,48 @@ def all_cases():
     out.append(Case(n, q, w, 2, False, 3, validate=True))
     n, batch, terms = HOST
     out += [Case(n, q, w, terms, False, batch) for q in moduli_at(n) for w in D.word_options(q)]
+    out += [f.case for f in footprint_cases()]
     return out
+
+
+# The caller's memory (tests/test_gpu_footprint.py): the smallest and the largest n, terms 3,
+# batch 1 and 33 (one live polynomial in the last block of 16 at n = 256), shared and per-batch
+# b_hat, one modulus per class in every word width; the host forms at the same n with batch 3.
+# host: "" for nttmul_mac_ntt_device, "host" for nttmul_mac_ntt_u32 / _u64.
+Footprint = namedtuple("Footprint", "entry case host", defaults=("",))
+FP_N = (256, 4096)
+FP_TERMS = 3
+FP_BATCHES = (1, 33)
+FP_HOST_BATCH = 3
+
+
+def footprint_cases():
+    out = []
+    for n in FP_N:
+        for q in moduli_at(n):
+            for w in D.word_options(q):
+                out += [Footprint("nttmul_mac_ntt_device", Case(n, q, w, FP_TERMS, s, batch))
+                        for batch in FP_BATCHES for s in (False, True)]
+                out += [Footprint(f"nttmul_mac_ntt_u{w}", Case(n, q, w, FP_TERMS, s, FP_HOST_BATCH),
+                                  "host") for s in (False, True)]
+    return out
+
+
+def units_per_block(case):
+    """{kernel_key: (polynomials per workgroup, polynomials of the launch, words per polynomial)}:
+    k_mac takes PB = 256 / (n / 16) output polynomials per 256-thread workgroup
+    (csrc/mac_dev.hpp:52, `live` :56); the range check one word per thread."""
+    io = "u32" if case.word_bits == 32 else "u64"
+    out = {mac_kernel(case.n, case.q, case.word_bits): (256 // (case.n // 16), case.batch, case.n)}
+    if case.validate:
+        out[f"k_check_range<{io}>"] = (256, case.batch * case.terms * case.n, 1)
+    return out
+
+
+def fp_guard_words(case):
+    """The guard width tests/guarded.py gives the call: a's batch entry is terms * n words."""
+    from guarded import guard_words
+    return guard_words(case.terms * case.n)
 
 
 # ---------------------------------------------------------------------------------------------

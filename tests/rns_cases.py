@@ -77,7 +77,63 @@ def all_cases():
     out += [Case(op, n, m, 5, 2 if op == "mac" else 1) for op in OPS]
     out += [Case(op, n, m, HOST_BATCH, HOST_TERMS if op == "mac" else 1, s)
             for n, m in HOST for op, s in [(o, False) for o in OPS] + [("mac", True)]]
+    out += [f.case for f in footprint_cases()]
     return out
+
+
+# The caller's memory (tests/test_gpu_footprint.py): product, both transforms and the mac at three
+# n (1024 and 4096 on 32-bit words take the descriptor path, with the limb in the span base),
+# L = 3, both word classes, batch 1 and 33; the transforms also in place; the host forms with
+# batch 3.  alias: "" or "out=in"; host: "" for a *_device call, "host" for the host form.
+Footprint = namedtuple("Footprint", "entry case alias host", defaults=("", ""))
+FP_N = (256, 1024, 4096)
+FP_BATCHES = (1, 33)
+FP_TERMS = 3
+FP_HOST_BATCH = 3
+ENTRY = {"multiply": "nttmul_rns_multiply", "forward": "nttmul_rns_forward",
+         "inverse": "nttmul_rns_inverse", "mac": "nttmul_rns_mac_ntt"}
+
+
+def footprint_cases():
+    out = []
+    for n in FP_N:
+        for m in BASES:
+            for batch in FP_BATCHES:
+                out += [Footprint(ENTRY[op] + "_device", Case(op, n, m, batch)) for op in OPS[:3]]
+                out += [Footprint(ENTRY["mac"] + "_device", Case("mac", n, m, batch, FP_TERMS, s))
+                        for s in (False, True)]
+                out += [Footprint(ENTRY[op] + "_device", Case(op, n, m, batch), "out=in")
+                        for op in ("forward", "inverse")]
+            out += [Footprint(ENTRY[op], Case(op, n, m, FP_HOST_BATCH), host="host")
+                    for op in OPS[:3]]
+            out += [Footprint(ENTRY["mac"], Case("mac", n, m, FP_HOST_BATCH, FP_TERMS, s),
+                              host="host") for s in (False, True)]
+    return out
+
+
+def units_per_block(case):
+    """{kernel_key: (polynomials per workgroup and limb, polynomials of the launch, words per
+    polynomial and limb)}; the limb is a grid dimension (csrc/rns.hip:57).  k_rns_rows:
+    rows_threads(LOGS) / (n / 16), with rows_threads(10) = 64, else 256 (csrc/rns_dev.hpp:45,
+    `live` :51; rns.hip:70); k_rns_xform: 256 / (n / 16) thread groups of xform_upg = 2
+    polynomials on 32-bit words, else 1 (rns_dev.hpp:116, :118, `live` / `live2` :126;
+    rns.hip:80); k_rns_mac: 256 / (n / 16) (rns_dev.hpp:178, `live` :184; rns.hip:91)."""
+    n = case.n
+    tp = n // 16
+    if case.op == "multiply":
+        upb = (64 if n == 1024 else 256) // tp
+    elif case.op in ("forward", "inverse"):
+        upb = 256 // tp * (2 if word_bits(case.moduli) == 32 else 1)
+    else:
+        upb = 256 // tp
+    return {rns_kernel(case.op, n, case.moduli): (upb, case.batch, n)}
+
+
+def fp_guard_words(case):
+    """The guard width tests/guarded.py gives the call: the widest batch entry is
+    terms * limbs * n words."""
+    from guarded import guard_words
+    return guard_words(case.terms * len(case.moduli) * case.n)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import pytest
 
 import bconv_cases as B
 import bconv_ref as R
+import guarded as G
 import nttmul
 
 pytestmark = pytest.mark.gpu
@@ -30,20 +31,19 @@ def _dt(bits):
     return np.uint32 if bits == 32 else np.uint64
 
 
-def _to_dev(torch, x, bits):
-    x = np.ascontiguousarray(x, dtype=_dt(bits))
-    return torch.from_numpy(x.view(np.int32 if bits == 32 else np.int64).reshape(-1)).cuda()
-
-
 def _call(torch, conv, op, x, stream=0):
-    """One device call on a numpy operand; returns (result, the operand after the call)."""
+    """One device call on a numpy operand, out of a guarded arena (tests/guarded.py: both operands
+    between sentinel guards, aligned to their word only; after the call no guard word and no
+    input word has changed and every output word is written); returns (result, the operand after
+    the call)."""
     bits, batch = conv.word_bits, x.shape[0]
-    dx = _to_dev(torch, x, bits)
-    out = torch.full((batch * conv.to_limbs * conv.n,), -1, dtype=dx.dtype, device="cuda")
+    arena = G.DeviceArena(torch, bits, G.guard_words(x.size // batch),
+                          out=batch * conv.to_limbs * conv.n, x=x)
+    out, dx = arena["out"], arena["x"]
     getattr(conv, f"{op}_device")(out, dx, batch, stream=stream)
     torch.cuda.synchronize()
-    return (out.cpu().numpy().view(_dt(bits)).reshape(batch, conv.to_limbs, conv.n),
-            dx.cpu().numpy().view(_dt(bits)).reshape(x.shape))
+    arena.check()
+    return arena.get("out", (batch, conv.to_limbs, conv.n)), arena.get("x", x.shape)
 
 
 def _input(op, bits, from_q, to_q, batch, n, seed):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import dispatch_cases as D
+import guarded as G
 import mac_cases as M
 import nttmul
 from oracle import oracle as O
@@ -31,19 +32,19 @@ def _to_dev(torch, x, bits):
     return torch.from_numpy(x.view(np.int32 if bits == 32 else np.int64).reshape(-1)).cuda()
 
 
-def _from_dev(t, bits, shape):
-    return t.cpu().numpy().view(_dt(bits)).reshape(shape).astype(np.uint64)
-
-
 def _mac_device(torch, ctx, a, b_hat, shared, bits, stream=0):
-    """One nttmul_mac_ntt_device call on numpy operands; returns (c, a after, b_hat after)."""
+    """One nttmul_mac_ntt_device call on numpy operands, out of a guarded arena
+    (tests/guarded.py: every operand between sentinel guards, aligned to its word only; after the
+    call no guard word and no input word has changed and every word of c is written); returns
+    (c, a after, b_hat after)."""
     batch, terms, n = a.shape
-    da, db = _to_dev(torch, a, bits), _to_dev(torch, b_hat, bits)
-    dc = torch.empty(batch * n, dtype=da.dtype, device="cuda")
+    arena = G.DeviceArena(torch, bits, G.guard_words(terms * n), c=batch * n, a=a, b_hat=b_hat)
+    dc, da, db = arena["c"], arena["a"], arena["b_hat"]
     ctx.mac_ntt_device(dc, da, db, batch, terms, bits, shared=shared, stream=stream)
     torch.cuda.synchronize()
-    return (_from_dev(dc, bits, (batch, n)), _from_dev(da, bits, a.shape),
-            _from_dev(db, bits, b_hat.shape))
+    arena.check()
+    return tuple(arena.get(k, shape).astype(np.uint64)
+                 for k, shape in (("c", (batch, n)), ("a", a.shape), ("b_hat", b_hat.shape)))
 
 
 def _sum_mod(rows, q):

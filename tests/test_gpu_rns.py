@@ -13,6 +13,7 @@ import functools
 import numpy as np
 import pytest
 
+import guarded as G
 import nttmul
 import rns_cases as R
 from oracle import oracle as O
@@ -39,17 +40,20 @@ def _to_dev(torch, x, bits):
     return torch.from_numpy(x.view(np.int32 if bits == 32 else np.int64).reshape(-1)).cuda()
 
 
-def _from_dev(t, bits, shape):
-    return t.cpu().numpy().view(_dt(bits)).reshape(shape).astype(np.uint64)
-
-
 def _call(torch, ctx, op, a, b=None, shared=False, stream=0, in_place=False):
-    """One device call on numpy operands; returns (result, operands after the call)."""
+    """One device call on numpy operands, out of a guarded arena (tests/guarded.py: every operand
+    between sentinel guards, aligned to its word only; after the call no guard word and no input
+    has changed and every output word is written); returns (result, operands after the call)."""
     bits = ctx.word_bits
     batch = a.shape[0]
-    da = _to_dev(torch, a, bits)
-    db = None if b is None else _to_dev(torch, b, bits)
-    dc = da if in_place else torch.empty(batch * ctx.limbs * ctx.n, dtype=da.dtype, device="cuda")
+    words = batch * ctx.limbs * ctx.n
+    operands = dict(a=a) if b is None else dict(a=a, b=b)
+    if not in_place:
+        operands["c"] = words
+    guard = G.guard_words(a.size // batch, 0 if b is None else b.size // (1 if shared else batch))
+    arena = G.DeviceArena(torch, bits, guard, inplace=("a",) if in_place else (), **operands)
+    da, db = arena["a"], None if b is None else arena["b"]
+    dc = da if in_place else arena["c"]
     if op == "multiply":
         ctx.multiply_device(dc, da, db, batch, stream=stream)
     elif op == "forward":
@@ -59,8 +63,9 @@ def _call(torch, ctx, op, a, b=None, shared=False, stream=0, in_place=False):
     else:
         ctx.mac_ntt_device(dc, da, db, batch, a.shape[1], shared=shared, stream=stream)
     torch.cuda.synchronize()
-    after = [_from_dev(da, bits, a.shape)] + ([] if b is None else [_from_dev(db, bits, b.shape)])
-    return _from_dev(dc, bits, (batch, ctx.limbs, ctx.n)), after
+    arena.check()
+    after = [arena.get(k, x.shape).astype(np.uint64) for k, x in (("a", a), ("b", b)) if x is not None]
+    return arena.get("a" if in_place else "c", (batch, ctx.limbs, ctx.n)).astype(np.uint64), after
 
 
 def _sum_mod(rows, q):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import dispatch_cases as D
+import guarded as G
 import nttmul
 from oracle import oracle as O
 from test_gpu_parity import (_as_np, _check_whole_batch, _random_primes, _xf_expected,  # noqa: F401
@@ -21,6 +22,21 @@ pytestmark = pytest.mark.gpu
 def _mulmod_rows(x, y, q):
     """x * y mod q elementwise with Python integers."""
     return ((x.astype(object) * y.astype(object)) % q).astype(np.uint64)
+
+
+def _guarded_host(ctx, entry, dt, x, y=None, mode=None):
+    """One host-buffer call (nttmul_transform_batch_* with `mode`, nttmul_pointwise_batch_* with
+    y) whose operands and result live in a guarded arena (tests/guarded.py: between sentinel
+    guards, aligned to their word only): after the call no guard word and no input word has
+    changed and every output word is written.  Returns the result in x's shape."""
+    bits = 32 if dt == np.uint32 else 64
+    operands = dict(out=x.size, x=x) if y is None else dict(out=x.size, x=x, y=y)
+    arena = G.HostArena(bits, G.guard_words(ctx.n), **operands)
+    fn = getattr(ctx._lib, f"{entry}_u{bits}")
+    ptrs = [arena[k].ctypes.data for k in operands]
+    ctx._check(fn(ctx._h, *([] if mode is None else [mode]), *ptrs, x.shape[0]))
+    arena.check()
+    return arena.get("out", x.shape)
 
 
 def test_named_moduli_are_what_the_tables_say(torch_cuda):
@@ -106,10 +122,10 @@ def test_transform_modes_every_size_and_word(n, q, cyclic, torch_cuda):
         for batch in D.XF_SWEEP_BATCHES:
             xs, ys = x[:batch].astype(dt), y[:batch].astype(dt)
             for m in D.XF_MODES:
-                got = ctx.transform(xs, m, dtype=dt)
+                got = _guarded_host(ctx, "nttmul_transform_batch", dt, xs, mode=m)
                 assert got.dtype == dt
                 assert np.array_equal(got.astype(np.uint64), exp[m][:batch]), (bits, batch, m)
-            got = ctx.pointwise(xs, ys, dtype=dt)
+            got = _guarded_host(ctx, "nttmul_pointwise_batch", dt, xs, ys)
             assert np.array_equal(got.astype(np.uint64), pw[:batch]), (bits, batch, "pointwise")
 
 
@@ -125,8 +141,11 @@ def test_device_path_in_u64_words(n, q, batch, torch_cuda):
     torch = torch_cuda
     P = O.Plan(n, q)
     ctx = nttmul.Context(n, q)
-    a = torch.empty(batch * n, dtype=torch.int64, device="cuda")
-    b, c, fa, fb, pw, c2, r = (torch.empty_like(a) for _ in range(7))
+    # every buffer is an output of some call, between sentinel guards and 8-byte aligned only
+    # (tests/guarded.py); that a and b stay what the fill wrote is part of _check_whole_batch
+    names = ("a", "b", "c", "fa", "fb", "pw", "c2", "r")
+    arena = G.DeviceArena(torch, 64, G.guard_words(n), **{k: batch * n for k in names})
+    a, b, c, fa, fb, pw, c2, r = (arena[k] for k in names)
     s = torch.cuda.current_stream().cuda_stream
     ctx.fill_random_device(a, b, 0, batch, 64, stream=s)
     ctx.multiply_device(c, a, b, batch, 64, stream=s)
@@ -139,6 +158,7 @@ def test_device_path_in_u64_words(n, q, batch, torch_cuda):
     ctx.inverse_device(c2, pw, batch, 64, stream=s)
     ctx.transform_device(r, a, nttmul.XF_REV2STD, batch, 64, stream=s)
     torch.cuda.synchronize()
+    arena.check()
     assert _check_whole_batch(n, q, 64, 0, batch, a, b, c) == batch
     assert torch.equal(c2, c)
     ha, hfa, hfb, hpw, hr = (_as_np(t, 64).reshape(batch, n) for t in (a, fa, fb, pw, r))
