@@ -27,6 +27,12 @@
  * A context is used by one host thread at a time; separate contexts are independent.  There is no
  * CPU fallback: without a usable HIP device nttmul_create fails with NTTMUL_ENODEV.
  *
+ * Lifetime.  A context serves any sequence of calls (tests/test_gpu_lifetime.py).  nttmul_destroy
+ * waits for the context's own streams and for the last call that went through its scratch, then
+ * frees the tables and the scratch; it does not wait for the streams the caller passed to the
+ * *_device calls.  Synchronise those streams (or the device) before nttmul_destroy: a kernel still
+ * queued on one of them would read freed tables.
+ *
  * Caller memory (host and device buffers alike; tests/test_gpu_footprint.py):
  *   Alignment.  Operands need the alignment of their word only (4 bytes for 32-bit words, 8 for
  *     64-bit words): every kernel touches caller memory one word per lane.
@@ -119,7 +125,8 @@ int nttmul_create_ex(nttmul_ctx **ctx, const nttmul_params *params);
  * the knobs.  NTTMUL_EINVAL for params_size below NTTMUL_PARAMS_BASE_SIZE or above the size this
  * library knows (fields it could not honour). */
 int nttmul_create_sized(nttmul_ctx **ctx, const nttmul_params *params, size_t params_size);
-/* ≙ PCIE_Close + PCIE_Unload */
+/* ≙ PCIE_Close + PCIE_Unload.  Work enqueued on the caller's own streams must have completed
+ * (Lifetime, above): destroy does not wait for it. */
 void nttmul_destroy(nttmul_ctx *ctx);
 
 const char *nttmul_strerror(int status);

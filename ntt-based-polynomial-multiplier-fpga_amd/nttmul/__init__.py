@@ -451,7 +451,11 @@ class Context:
     transform (forward, inverse, transform in every mode), and c may be a or b for pointwise; for
     products c must not overlap a or b; partial overlap is never allowed.  Footprint: a call
     writes exactly batch * n words of its output and nothing else in caller memory; inputs are
-    never written."""
+    never written.
+
+    Lifetime: one context serves any sequence of calls, from one host thread at a time.  close()
+    (nttmul_destroy) does not wait for the streams passed to the *_device calls: synchronise them
+    first, a kernel still queued there would read freed tables."""
 
     def __init__(self, n: int, q: int, psi: int = 0, ndev: int = 1, first_dev: int = 0,
                  validate: bool = False, cyclic: bool = False, share_devices: bool = False,

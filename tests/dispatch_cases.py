@@ -518,6 +518,9 @@ def new_cases():
                     Case("transform", n, q, w, n.bit_length(), mode=3)]
     out.append(Case("multiply", SAT_SERVER[0], SAT_SERVER[1], 32, 1, path="server"))
     out += [f.case for f in footprint_cases()]
+    # the launches of the call sequences over long-lived contexts (tests/test_gpu_lifetime.py)
+    from lifetime_cases import lifetime_cases
+    out += lifetime_cases()
     return out
 
 
