@@ -50,7 +50,8 @@
  * issues oldest-first.
  *
  * Out of scope here:
- *   - n > 4096 (the column passes of the multi-pass product are not limb-aware);
+ *   - n > 4096 (the column passes of the multi-pass product are not limb-aware); that is
+ *     include/nttmul_rnsmp.h, lib/libnttmul_rnsmp.so;
  *   - 64-bit storage of 32-bit limbs, and the class 2^31 <= q < 2^32;
  *   - CRT reconstruction (base conversion between bases: include/nttmul_bconv.h,
  *     lib/libnttmul_bconv.so);

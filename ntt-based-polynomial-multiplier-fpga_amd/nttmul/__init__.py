@@ -1109,6 +1109,219 @@ class BaseConverter:
         return self._host("moddown", x)
 
 
+# ---- limb-aware multi-pass RNS, 4096 < n <= 65536 (include/nttmul_rnsmp.h) ----------------------
+
+RNSMP_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_rnsmp.so")
+RNSMP_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_rnsmp.h")
+RNSMP_N = (8192, 16384, 32768, 65536)
+
+_RNSMP_LIB: Optional[ctypes.CDLL] = None
+
+
+class RnsMpInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("limbs", ctypes.c_uint32),
+                ("word_bits", ctypes.c_uint32), ("ndev", ctypes.c_int),
+                ("scratch_mb", ctypes.c_uint32)]
+
+
+def load_rnsmp_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_rnsmp.so (include/nttmul_rnsmp.h): the ABI and kernels of
+    libnttmul_bconv.so plus the limb-aware multi-pass kernels.  The other loaders are
+    unaffected."""
+    global _RNSMP_LIB
+    if _RNSMP_LIB is not None:
+        return _RNSMP_LIB
+    if not os.path.exists(RNSMP_LIB_PATH):
+        raise ImportError(f"{RNSMP_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
+    lib = _bind_rns(_bind_mac(_bind(ctypes.CDLL(RNSMP_LIB_PATH))))
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    lib.nttmul_rnsmp_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(_Params), sz,
+                                        ctypes.POINTER(ctypes.c_uint64), u32]
+    lib.nttmul_rnsmp_destroy.argtypes = [vp]
+    lib.nttmul_rnsmp_destroy.restype = None
+    lib.nttmul_rnsmp_last_error.argtypes = [vp]
+    lib.nttmul_rnsmp_last_error.restype = ctypes.c_char_p
+    lib.nttmul_rnsmp_get_info.argtypes = [vp, ctypes.POINTER(RnsMpInfo)]
+    lib.nttmul_rnsmp_limb_info.argtypes = [vp, u32, ctypes.POINTER(Info)]
+    lib.nttmul_rnsmp_multiply_device.argtypes = [vp, vp, vp, vp, sz, i32, vp]
+    lib.nttmul_rnsmp_forward_device.argtypes = [vp, vp, vp, sz, i32, vp]
+    lib.nttmul_rnsmp_inverse_device.argtypes = [vp, vp, vp, sz, i32, vp]
+    lib.nttmul_rnsmp_mac_ntt_device.argtypes = [vp, vp, vp, vp, sz, u32, i32, i32, vp]
+    lib.nttmul_rnsmp_multiply.argtypes = [vp, vp, vp, vp, sz]
+    lib.nttmul_rnsmp_forward.argtypes = [vp, vp, vp, sz]
+    lib.nttmul_rnsmp_inverse.argtypes = [vp, vp, vp, sz]
+    lib.nttmul_rnsmp_mac_ntt.argtypes = [vp, vp, vp, vp, sz, u32, i32]
+    lib.nttmul_rnsmp_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
+    _RNSMP_LIB = lib
+    return lib
+
+
+def rnsmp_exported_symbols() -> list:
+    """Function names declared in include/nttmul_rnsmp.h."""
+    import re
+    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_rnsmp_\w+)\s*\(",
+                                 open(RNSMP_HEADER_PATH).read(), re.M)))
+
+
+class RnsMpContext:
+    """nttmul_rnsmp: the moduli q_0 .. q_{L-1} of one degree n in 8192 .. 65536, every pass of
+    every operation one launch over [batch, limbs, n] operands (include/nttmul_rnsmp.h; n <= 4096
+    is RnsContext's).  Words are info.word_bits wide: 32 when every q_l < 2^31, 64 when every
+    q_l >= 2^32.  scratch_mb: MiB per scratch buffer (0 = the library default, 512); larger
+    batches run in sub-batches of whole polynomials.
+
+    Caller memory, as for RnsContext: operands need the alignment of their word only; out may be
+    the input itself for forward and inverse, c must not overlap a, b or b_hat, and partial
+    overlap is never allowed; a call writes exactly batch * limbs * n words of its output and
+    nothing else in caller memory, and never writes an input.
+
+    Lifetime: one context serves any sequence of calls on any streams, from one host thread at a
+    time (the scratch is handed between streams by an event).  close() does not wait for the
+    streams passed to the *_device calls: synchronise them first."""
+
+    def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False, scratch_mb: int = 0):
+        self._lib = load_rnsmp_library()
+        self._h = ctypes.c_void_p()
+        moduli = [int(q) for q in moduli]
+        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
+                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
+        prm = _Params(n, 0, 0, ndev, first_dev, flags, 0, 0, 0, scratch_mb, 0)
+        qs = (ctypes.c_uint64 * max(1, len(moduli)))(*moduli)
+        st = self._lib.nttmul_rnsmp_create(ctypes.byref(self._h), ctypes.byref(prm),
+                                           ctypes.sizeof(prm), qs, len(moduli))
+        if st != NTTMUL_OK:
+            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
+        info = RnsMpInfo()
+        self._lib.nttmul_rnsmp_get_info(self._h, ctypes.byref(info))
+        self.info = info
+        self.n, self.limbs, self.word_bits = info.n, info.limbs, info.word_bits
+        self.moduli = tuple(moduli)
+        self.first_dev = first_dev
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.nttmul_rnsmp_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, st: int):
+        if st != NTTMUL_OK:
+            raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
+                                  f"{self._lib.nttmul_rnsmp_last_error(self._h).decode()}")
+
+    @property
+    def io_dtype(self):
+        return np.uint32 if self.word_bits == 32 else np.uint64
+
+    def limb_info(self, limb: int) -> Info:
+        """nttmul_rnsmp_limb_info: q, psi, omega, ... of one limb."""
+        info = Info()
+        self._check(self._lib.nttmul_rnsmp_limb_info(self._h, limb, ctypes.byref(info)))
+        return info
+
+    def kernel_name(self, op) -> str:
+        """nttmul_rnsmp_kernel_name for op 0..3 or "multiply" / "forward" / "inverse" / "mac": the
+        launch sequence, e.g. "k_rnsmp_cols_fwd<Arith64,u64,4,1> + k_rnsmp_xform<Arith64,u64,4,0>"."""
+        op = RNS_OPS.index(op) if isinstance(op, str) else int(op)
+        buf = ctypes.create_string_buffer(512)
+        st = self._lib.nttmul_rnsmp_kernel_name(self._h, op, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    # device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`
+
+    def _dev_args(self, operands, polys, dev):
+        return [_dev_arg(t, k * self.limbs, self.n, self.word_bits, dev)
+                for t, k in zip(operands, polys)]
+
+    def multiply_device(self, c, a, b, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """c, a, b: [batch][limbs][n]."""
+        dev = self.first_dev if dev is None else dev
+        args = self._dev_args((c, a, b), (batch,) * 3, dev)
+        self._check(self._lib.nttmul_rnsmp_multiply_device(self._h, *args, batch, dev, stream or None))
+
+    def forward_device(self, out, a, batch: int, dev: Optional[int] = None, stream: int = 0):
+        dev = self.first_dev if dev is None else dev
+        args = self._dev_args((out, a), (batch,) * 2, dev)
+        self._check(self._lib.nttmul_rnsmp_forward_device(self._h, *args, batch, dev, stream or None))
+
+    def inverse_device(self, out, a, batch: int, dev: Optional[int] = None, stream: int = 0):
+        dev = self.first_dev if dev is None else dev
+        args = self._dev_args((out, a), (batch,) * 2, dev)
+        self._check(self._lib.nttmul_rnsmp_inverse_device(self._h, *args, batch, dev, stream or None))
+
+    def mac_ntt_device(self, c, a, b_hat, batch: int, terms: int, shared: bool = False,
+                       dev: Optional[int] = None, stream: int = 0):
+        """a [batch][terms][limbs][n], b_hat likewise ([terms][limbs][n] when shared),
+        c [batch][limbs][n]."""
+        dev = self.first_dev if dev is None else dev
+        args = self._dev_args((c, a, b_hat),
+                              (batch, batch * terms, terms if shared else batch * terms), dev)
+        self._check(self._lib.nttmul_rnsmp_mac_ntt_device(self._h, *args, batch, terms,
+                                                          int(shared), dev, stream or None))
+
+    # host arrays
+
+    def _host(self, x, ndim, what):
+        x = np.ascontiguousarray(x, dtype=self.io_dtype)
+        if x.ndim != ndim or x.shape[-2:] != (self.limbs, self.n):
+            raise ValueError(f"{what} must have shape "
+                             f"[batch, {'terms, ' if ndim == 4 else ''}limbs, n]")
+        return x
+
+    def multiply(self, a, b) -> np.ndarray:
+        """c[p][l] = a[p][l] * b[p][l] mod (x^n + 1, q_l) for arrays of shape [batch, limbs, n]."""
+        a, b = self._host(a, 3, "a"), self._host(b, 3, "b")
+        if a.shape != b.shape:
+            raise ValueError("a and b must have the same shape")
+        c = np.empty_like(a)
+        self._check(self._lib.nttmul_rnsmp_multiply(self._h, c.ctypes.data, a.ctypes.data,
+                                                    b.ctypes.data, a.shape[0]))
+        return c
+
+    def forward(self, a) -> np.ndarray:
+        a = self._host(a, 3, "a")
+        out = np.empty_like(a)
+        self._check(self._lib.nttmul_rnsmp_forward(self._h, out.ctypes.data, a.ctypes.data,
+                                                   a.shape[0]))
+        return out
+
+    def inverse(self, a_hat) -> np.ndarray:
+        a_hat = self._host(a_hat, 3, "a_hat")
+        out = np.empty_like(a_hat)
+        self._check(self._lib.nttmul_rnsmp_inverse(self._h, out.ctypes.data, a_hat.ctypes.data,
+                                                   a_hat.shape[0]))
+        return out
+
+    def mac_ntt(self, a, b_hat, shared: bool = False) -> np.ndarray:
+        """a of shape [batch, terms, limbs, n]; b_hat of a's shape, or [terms, limbs, n] when
+        shared.  Returns c of shape [batch, limbs, n]."""
+        a = self._host(a, 4, "a")
+        b_hat = np.ascontiguousarray(b_hat, dtype=self.io_dtype)
+        if a.shape[1] == 0:
+            raise ValueError("terms must be > 0")
+        if b_hat.shape != (a.shape[1:] if shared else a.shape):
+            raise ValueError("b_hat must have a's shape, or [terms, limbs, n] when shared")
+        c = np.empty((a.shape[0], self.limbs, self.n), dtype=self.io_dtype)
+        self._check(self._lib.nttmul_rnsmp_mac_ntt(self._h, c.ctypes.data, a.ctypes.data,
+                                                   b_hat.ctypes.data, a.shape[0], a.shape[1],
+                                                   int(shared)))
+        return c
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
