@@ -1322,6 +1322,217 @@ class RnsMpContext:
         return c
 
 
+# ---- Galois automorphisms over all RNS limbs (include/nttmul_galois.h) ---------------------------
+
+GALOIS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_galois.so")
+GALOIS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_galois.h")
+GALOIS_OPS = ("coeff", "ntt", "ntt_many")             # nttmul_galois_kernel_name's op numbers
+GALOIS_MAX_COUNT = 16
+
+_GALOIS_LIB: Optional[ctypes.CDLL] = None
+
+
+class GaloisInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("limbs", ctypes.c_uint32),
+                ("word_bits", ctypes.c_uint32), ("ndev", ctypes.c_int)]
+
+
+def load_galois_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_galois.so (include/nttmul_galois.h): the ABI and kernels of
+    libnttmul_rnsmp.so plus the automorphism kernels.  The other loaders are unaffected."""
+    global _GALOIS_LIB
+    if _GALOIS_LIB is not None:
+        return _GALOIS_LIB
+    if not os.path.exists(GALOIS_LIB_PATH):
+        raise ImportError(f"{GALOIS_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
+    lib = _bind_rns(_bind_mac(_bind(ctypes.CDLL(GALOIS_LIB_PATH))))
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u32p = ctypes.POINTER(u32)
+    lib.nttmul_galois_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(_Params), sz,
+                                         ctypes.POINTER(ctypes.c_uint64), u32]
+    lib.nttmul_galois_destroy.argtypes = [vp]
+    lib.nttmul_galois_destroy.restype = None
+    lib.nttmul_galois_last_error.argtypes = [vp]
+    lib.nttmul_galois_last_error.restype = ctypes.c_char_p
+    lib.nttmul_galois_get_info.argtypes = [vp, ctypes.POINTER(GaloisInfo)]
+    lib.nttmul_galois_limb_info.argtypes = [vp, u32, ctypes.POINTER(Info)]
+    lib.nttmul_galois_element.argtypes = [u32, ctypes.c_int64, i32, u32p]
+    lib.nttmul_galois_plan.argtypes = [u32, u32, vp, vp, vp]
+    lib.nttmul_galois_coeff_device.argtypes = [vp, vp, vp, u32, sz, i32, vp]
+    lib.nttmul_galois_ntt_device.argtypes = [vp, vp, vp, u32, sz, i32, vp]
+    lib.nttmul_galois_ntt_many_device.argtypes = [vp, vp, vp, u32p, u32, sz, i32, vp]
+    lib.nttmul_galois_coeff.argtypes = [vp, vp, vp, u32, sz]
+    lib.nttmul_galois_ntt.argtypes = [vp, vp, vp, u32, sz]
+    lib.nttmul_galois_kernel_name.argtypes = [vp, i32, u32, ctypes.c_char_p, sz]
+    _GALOIS_LIB = lib
+    return lib
+
+
+def galois_exported_symbols() -> list:
+    """Function names declared in include/nttmul_galois.h."""
+    import re
+    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_galois_\w+)\s*\(",
+                                 open(GALOIS_HEADER_PATH).read(), re.M)))
+
+
+def galois_element(n: int, step: int, conjugate: bool = False) -> int:
+    """nttmul_galois_element: k = 5^step mod 2n (a negative step: powers of 5^-1), times 2n - 1
+    when conjugate.  Host only."""
+    lib = load_galois_library()
+    k = ctypes.c_uint32()
+    st = lib.nttmul_galois_element(n, step, int(conjugate), ctypes.byref(k))
+    if st != NTTMUL_OK:
+        raise NttmulError(st, lib.nttmul_strerror(st).decode())
+    return k.value
+
+
+def galois_plan(n: int, k: int):
+    """nttmul_galois_plan: (coeff_src, coeff_neg, ntt_src), the index tables the kernels compute
+    per lane: out[j] = (-in if coeff_neg[j] else in)[coeff_src[j]] in coefficient order,
+    out_hat[j] = in_hat[ntt_src[j]] in NTT order.  Host only."""
+    lib = load_galois_library()
+    if not 0 <= n < 1 << 32 or not 0 <= k < 1 << 32:
+        raise NttmulError(NTTMUL_EINVAL, lib.nttmul_strerror(NTTMUL_EINVAL).decode())
+    size = n if 256 <= n <= 65536 else 1
+    src, neg, hat = (np.zeros(size, dtype=np.uint32), np.zeros(size, dtype=np.uint8),
+                     np.zeros(size, dtype=np.uint32))
+    st = lib.nttmul_galois_plan(n, k, src.ctypes.data, neg.ctypes.data, hat.ctypes.data)
+    if st != NTTMUL_OK:
+        raise NttmulError(st, lib.nttmul_strerror(st).decode())
+    return src, neg, hat
+
+
+class GaloisContext:
+    """nttmul_galois: the automorphisms sigma_k : a(x) -> a(x^k) mod (x^n + 1), k odd, over the
+    moduli q_0 .. q_{L-1} of one degree n in 256 .. 65536, each call one launch over
+    [batch, limbs, n] operands (include/nttmul_galois.h).  coeff_*: coefficient order, canonical
+    outputs; ntt_*: the bit-reversed canonical transforms RnsContext / RnsMpContext.forward write
+    and mac_ntt reads as b_hat.  Words are info.word_bits wide: 32 when every q_l < 2^31, 64 when
+    every q_l >= 2^32.
+
+    Caller memory: operands need the alignment of their word only; out must not overlap the input
+    (no in-place form); a call writes exactly count * batch * limbs * n words of its output and
+    nothing else in caller memory, and never writes an input.
+
+    close() does not wait for the streams passed to the *_device calls: synchronise them first."""
+
+    def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False):
+        self._lib = load_galois_library()
+        self._h = ctypes.c_void_p()
+        moduli = [int(q) for q in moduli]
+        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
+                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
+        prm = _Params(n, 0, 0, ndev, first_dev, flags, 0, 0, 0, 0, 0)
+        qs = (ctypes.c_uint64 * max(1, len(moduli)))(*moduli)
+        st = self._lib.nttmul_galois_create(ctypes.byref(self._h), ctypes.byref(prm),
+                                            ctypes.sizeof(prm), qs, len(moduli))
+        if st != NTTMUL_OK:
+            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
+        info = GaloisInfo()
+        self._lib.nttmul_galois_get_info(self._h, ctypes.byref(info))
+        self.info = info
+        self.n, self.limbs, self.word_bits = info.n, info.limbs, info.word_bits
+        self.moduli = tuple(moduli)
+        self.first_dev = first_dev
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.nttmul_galois_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, st: int):
+        if st != NTTMUL_OK:
+            raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
+                                  f"{self._lib.nttmul_galois_last_error(self._h).decode()}")
+
+    @property
+    def io_dtype(self):
+        return np.uint32 if self.word_bits == 32 else np.uint64
+
+    def limb_info(self, limb: int) -> Info:
+        """nttmul_galois_limb_info: q, psi, omega, ... of one limb."""
+        info = Info()
+        self._check(self._lib.nttmul_galois_limb_info(self._h, limb, ctypes.byref(info)))
+        return info
+
+    def kernel_name(self, op, count: int = 1) -> str:
+        """nttmul_galois_kernel_name for op 0..2 or "coeff" / "ntt" / "ntt_many", e.g.
+        "k_galois_coeff<u32,0>"."""
+        op = GALOIS_OPS.index(op) if isinstance(op, str) else int(op)
+        buf = ctypes.create_string_buffer(128)
+        st = self._lib.nttmul_galois_kernel_name(self._h, op, count, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    # device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`
+
+    def _dev_args(self, operands, polys, dev):
+        return [_dev_arg(t, k * self.limbs, self.n, self.word_bits, dev)
+                for t, k in zip(operands, polys)]
+
+    def coeff_device(self, out, x, k: int, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """out = sigma_k(x) in coefficient order; out, x: [batch][limbs][n]."""
+        dev = self.first_dev if dev is None else dev
+        args = self._dev_args((out, x), (batch,) * 2, dev)
+        self._check(self._lib.nttmul_galois_coeff_device(self._h, *args, k, batch, dev,
+                                                         stream or None))
+
+    def ntt_device(self, out, x_hat, k: int, batch: int, dev: Optional[int] = None,
+                   stream: int = 0):
+        """out = sigma_k on bit-reversed transforms; out, x_hat: [batch][limbs][n]."""
+        dev = self.first_dev if dev is None else dev
+        args = self._dev_args((out, x_hat), (batch,) * 2, dev)
+        self._check(self._lib.nttmul_galois_ntt_device(self._h, *args, k, batch, dev,
+                                                       stream or None))
+
+    def ntt_many_device(self, out, x_hat, ks, batch: int, dev: Optional[int] = None,
+                        stream: int = 0):
+        """out[c] = sigma_{ks[c]}(x_hat) for every c in one launch; out
+        [len(ks)][batch][limbs][n], x_hat [batch][limbs][n]."""
+        dev = self.first_dev if dev is None else dev
+        ks = [int(k) for k in ks]
+        args = self._dev_args((out, x_hat), (batch * len(ks), batch), dev)
+        karr = (ctypes.c_uint32 * max(1, len(ks)))(*ks)
+        self._check(self._lib.nttmul_galois_ntt_many_device(self._h, *args, karr, len(ks), batch,
+                                                            dev, stream or None))
+
+    # host arrays
+
+    def _host(self, x, what):
+        x = np.ascontiguousarray(x, dtype=self.io_dtype)
+        if x.ndim != 3 or x.shape[-2:] != (self.limbs, self.n):
+            raise ValueError(f"{what} must have shape [batch, limbs, n]")
+        return x
+
+    def coeff(self, a, k: int) -> np.ndarray:
+        a = self._host(a, "a")
+        out = np.empty_like(a)
+        self._check(self._lib.nttmul_galois_coeff(self._h, out.ctypes.data, a.ctypes.data, k,
+                                                  a.shape[0]))
+        return out
+
+    def ntt(self, a_hat, k: int) -> np.ndarray:
+        a_hat = self._host(a_hat, "a_hat")
+        out = np.empty_like(a_hat)
+        self._check(self._lib.nttmul_galois_ntt(self._h, out.ctypes.data, a_hat.ctypes.data, k,
+                                                a_hat.shape[0]))
+        return out
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
