@@ -27,7 +27,9 @@ static hipError_t dispatch(const BconvTables &T, int op, void *out, const void *
 
 static hipError_t dispatch_words(const BconvTables &T, int op, void *out, const void *in,
                                  size_t batch, const Emit &E) {
-  if (T.logn < 8 || T.logn > 12 || !T.from_limbs || !T.to_limbs) return hipErrorInvalidValue;
+  // (nttmul_bconv_create stops at n = 4096 in bconv.cpp's validate; lib/libnttmul_ks.so's ModDown
+  // launches the same kernel up to n = 65536: k_bconv takes logn and 64-bit offsets)
+  if (T.logn < 8 || T.logn > 16 || !T.from_limbs || !T.to_limbs) return hipErrorInvalidValue;
   return T.word_bits == 32 ? dispatch<uint32_t>(T, op, out, in, batch, E)
                            : dispatch<uint64_t>(T, op, out, in, batch, E);
 }

@@ -1533,6 +1533,202 @@ class GaloisContext:
         return out
 
 
+# ---- digit ModUp and ModDown for hybrid key switching (include/nttmul_ks.h) ----------------------
+
+KS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_ks.so")
+KS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_ks.h")
+KS_OPS = ("modup", "moddown")                         # nttmul_ks_kernel_name's op numbers
+
+_KS_LIB: Optional[ctypes.CDLL] = None
+
+
+class KsInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("q_limbs", ctypes.c_uint32),
+                ("p_limbs", ctypes.c_uint32), ("digit_limbs", ctypes.c_uint32),
+                ("digits", ctypes.c_uint32), ("word_bits", ctypes.c_uint32),
+                ("ndev", ctypes.c_int)]
+
+
+def load_ks_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_ks.so (include/nttmul_ks.h): the ABI and kernels of libnttmul_galois.so
+    plus the digit ModUp kernel.  The other loaders are unaffected."""
+    global _KS_LIB
+    if _KS_LIB is not None:
+        return _KS_LIB
+    if not os.path.exists(KS_LIB_PATH):
+        raise ImportError(f"{KS_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
+    lib = _bind_rns(_bind_mac(_bind(ctypes.CDLL(KS_LIB_PATH))))
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u64p, prm = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_Params)
+    lib.nttmul_ks_create.argtypes = [ctypes.POINTER(vp), prm, sz, u64p, u32, u64p, u32, u32]
+    lib.nttmul_ks_destroy.argtypes = [vp]
+    lib.nttmul_ks_destroy.restype = None
+    lib.nttmul_ks_last_error.argtypes = [vp]
+    lib.nttmul_ks_last_error.restype = ctypes.c_char_p
+    lib.nttmul_ks_get_info.argtypes = [vp, ctypes.POINTER(KsInfo)]
+    lib.nttmul_ks_plan.argtypes = [prm, sz, u64p, u32, u64p, u32, u32] + [vp] * 6
+    for op in KS_OPS:
+        getattr(lib, f"nttmul_ks_{op}_device").argtypes = [vp, vp, vp, sz, i32, vp]
+        getattr(lib, f"nttmul_ks_{op}").argtypes = [vp, vp, vp, sz]
+    lib.nttmul_ks_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
+    _KS_LIB = lib
+    return lib
+
+
+def ks_exported_symbols() -> list:
+    """Function names declared in include/nttmul_ks.h."""
+    import re
+    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_ks_\w+)\s*\(",
+                                 open(KS_HEADER_PATH).read(), re.M)))
+
+
+def _ks_bases(n, q, p, flags):
+    q, p = [int(v) for v in q], [int(v) for v in p]
+    prm = _Params(n, 0, 0, 1, 0, flags, 0, 0, 0, 0, 0)
+    qa = (ctypes.c_uint64 * max(1, len(q)))(*q)
+    pa = (ctypes.c_uint64 * max(1, len(p)))(*p)
+    return q, p, prm, qa, pa
+
+
+def ks_plan(n: int, q, p, digit_limbs: int, flags: int = 0):
+    """nttmul_ks_plan, without a device: (inv, w, gadget, pinv, pw, Pinv) as lists of Python
+    integers, with M = len(q) + len(p) and m over the extended basis q_0 .., p_0 ..:
+    inv[i] = Dh_i^-1 mod q_i, w[i][m] = Dh_i mod m-th modulus, gadget[d][m] = the key generator's
+    factor of digit d mod m-th modulus, and (pinv, pw, Pinv) = bconv_plan(n, p, q).  Raises
+    NttmulError with the status nttmul_ks_create would return for these arguments."""
+    lib = load_ks_library()
+    q, p, prm, qa, pa = _ks_bases(n, q, p, flags)
+    L, K = len(q), len(p)
+    if not 0 <= digit_limbs < 1 << 32:
+        raise NttmulError(NTTMUL_EINVAL, lib.nttmul_strerror(NTTMUL_EINVAL).decode())
+    M = L + K
+    dnum = -(-L // digit_limbs) if 0 < digit_limbs <= L else 1
+    sizes = (L, L * M, dnum * M, K, K * L, L)
+    t = [(ctypes.c_uint64 * max(1, k))() for k in sizes]
+    st = lib.nttmul_ks_plan(ctypes.byref(prm), ctypes.sizeof(prm), qa, L, pa, K, digit_limbs,
+                            *(ctypes.addressof(x) for x in t))
+    if st != NTTMUL_OK:
+        raise NttmulError(st, lib.nttmul_strerror(st).decode())
+    inv, w, gadget, pinv, pw, Pinv = (list(x[:k]) for x, k in zip(t, sizes))
+    rows = lambda flat, width: [flat[i:i + width] for i in range(0, len(flat), width)]
+    return inv, rows(w, M), rows(gadget, M), pinv, rows(pw, L), Pinv
+
+
+class KeySwitchBasis:
+    """nttmul_ks: the bases Q = q (L primes) and P = p (K primes), disjoint and of one word class,
+    with digits of digit_limbs limbs of Q, for one degree n in 256 .. 65536
+    (include/nttmul_ks.h).  modup maps [batch, L, n] to [batch, digits, L + K, n], the operand `a`
+    of RnsContext / RnsMpContext.mac_ntt with terms = digits over the extended basis q + p;
+    moddown maps [batch, L + K, n] to [batch, L, n].  Coefficient order, canonical words of
+    info.word_bits.
+
+    Caller memory: operands need the alignment of their word only; out must not overlap the
+    input; modup writes exactly batch * digits * (L + K) * n words and moddown batch * L * n.
+
+    close() does not wait for the streams passed to the *_device calls: synchronise them first."""
+
+    def __init__(self, n: int, q, p, digit_limbs: int, ndev: int = 1, first_dev: int = 0,
+                 validate: bool = False, cyclic: bool = False, share_devices: bool = False):
+        self._lib = load_ks_library()
+        self._h = ctypes.c_void_p()
+        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
+                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
+        q, p, prm, qa, pa = _ks_bases(n, q, p, flags)
+        prm.ndev, prm.first_dev = ndev, first_dev
+        st = self._lib.nttmul_ks_create(ctypes.byref(self._h), ctypes.byref(prm),
+                                        ctypes.sizeof(prm), qa, len(q), pa, len(p), digit_limbs)
+        if st != NTTMUL_OK:
+            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
+        info = KsInfo()
+        self._lib.nttmul_ks_get_info(self._h, ctypes.byref(info))
+        self.info = info
+        self.n, self.word_bits = info.n, info.word_bits
+        self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
+        self.digit_limbs, self.digits = info.digit_limbs, info.digits
+        self.q, self.p = tuple(q), tuple(p)
+        self.first_dev = first_dev
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.nttmul_ks_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, st: int):
+        if st != NTTMUL_OK:
+            raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
+                                  f"{self._lib.nttmul_ks_last_error(self._h).decode()}")
+
+    @property
+    def io_dtype(self):
+        return np.uint32 if self.word_bits == 32 else np.uint64
+
+    def kernel_name(self, op) -> str:
+        """nttmul_ks_kernel_name for op 0..1 or "modup" / "moddown", e.g. "k_ks_modup<u32>"."""
+        op = KS_OPS.index(op) if isinstance(op, str) else int(op)
+        buf = ctypes.create_string_buffer(128)
+        st = self._lib.nttmul_ks_kernel_name(self._h, op, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def _limbs(self, op: str):
+        """(output, input) limb polynomials per batch entry."""
+        ext = self.q_limbs + self.p_limbs
+        return (self.digits * ext, self.q_limbs) if op == "modup" else (self.q_limbs, ext)
+
+    # device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`
+
+    def _device(self, op, out, x, batch, dev, stream):
+        dev = self.first_dev if dev is None else dev
+        args = [_dev_arg(t, batch * k, self.n, self.word_bits, dev)
+                for t, k in zip((out, x), self._limbs(op))]
+        fn = getattr(self._lib, f"nttmul_ks_{op}_device")
+        self._check(fn(self._h, *args, batch, dev, stream or None))
+
+    def modup_device(self, out, x, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """x [batch][L][n] -> out [batch][digits][L + K][n]."""
+        self._device("modup", out, x, batch, dev, stream)
+
+    def moddown_device(self, out, x, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """x [batch][L + K][n] -> out [batch][L][n]."""
+        self._device("moddown", out, x, batch, dev, stream)
+
+    # host arrays
+
+    def _host(self, op, x):
+        out_limbs, in_limbs = self._limbs(op)
+        x = np.ascontiguousarray(x, dtype=self.io_dtype)
+        if x.ndim != 3 or x.shape[1:] != (in_limbs, self.n):
+            raise ValueError(f"{op}: x must have shape [batch, {in_limbs}, {self.n}]")
+        out = np.empty((x.shape[0], out_limbs, self.n), dtype=self.io_dtype)
+        fn = getattr(self._lib, f"nttmul_ks_{op}")
+        self._check(fn(self._h, out.ctypes.data, x.ctypes.data, x.shape[0]))
+        return out
+
+    def modup(self, x) -> np.ndarray:
+        """out[p][d][m] = (sum over i in D_d of (x[p][i] Dh_i^-1 mod q_i) Dh_i) mod the m-th
+        modulus of q + p, for x of shape [batch, L, n]; returns [batch, digits, L + K, n]."""
+        out = self._host("modup", x)
+        return out.reshape(out.shape[0], self.digits, self.q_limbs + self.p_limbs, self.n)
+
+    def moddown(self, x) -> np.ndarray:
+        """out[p][i] = (x[p][i] - convert(x[p][L:])[i]) P^-1 mod q_i for x of shape
+        [batch, L + K, n]; returns [batch, L, n]."""
+        return self._host("moddown", x)
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
