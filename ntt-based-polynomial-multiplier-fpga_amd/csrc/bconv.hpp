@@ -1,6 +1,8 @@
 // bconv.hpp — internal interface between the host entry points of include/nttmul_bconv.h
 // (bconv.cpp) and the launchers of bconv.hip.  lib/libnttmul_bconv.so only.
 #pragma once
+#include <vector>
+
 #include "launch.hpp"
 
 namespace nttmul {
@@ -28,6 +30,22 @@ template <class W>
 struct BconvTo {
   W c, qinv_neg, cr, v, vs;
 };
+
+// The host side of the table format (bconv.cpp; ks.cpp builds its ModUp and ModDown tables with
+// the same functions).
+// (value, companion) pair the device multiplies by k with (bconv_dev.hpp mulc): the Plantard pair
+// of Arith32P::pmul, BR = B q^-1 mod 2^64 with B = -k 2^64 mod q as (low, high) word, or Shoup
+template <class W>
+void mul_pair(uint64_t k, uint64_t q, W *v, W *vs);
+// -q^-1 mod 2^64 (the low word serves 32-bit words)
+uint64_t neg_inv(uint64_t q);
+// The three device tables of a conversion for words of word_bits, in host memory: `from` limbs b
+// with the factors inv [|b|], `to` limbs c with the epilogue factors binv [|c|] and the weights
+// w [|b|][|c|]
+void build_tables(int word_bits, const std::vector<uint64_t> &b, const std::vector<uint64_t> &inv,
+                  const std::vector<uint64_t> &c, const std::vector<uint64_t> &binv,
+                  const std::vector<uint64_t> &w, std::vector<uint8_t> *from,
+                  std::vector<uint8_t> *to, std::vector<uint8_t> *wt);
 
 // Per-device view of a converter: what a launch needs (pointers are device memory).
 struct BconvTables {

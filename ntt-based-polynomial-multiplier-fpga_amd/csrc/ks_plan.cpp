@@ -1,58 +1,42 @@
 // ks_plan.cpp — the host-only part of include/nttmul_ks.h (lib/libnttmul_ks.so only):
 // nttmul_ks_plan, and the validation and plain constants ks.cpp shares with it.  The constants
 // come from the planner's modular arithmetic (planner.hpp mulmod / powmod) in 128-bit host
-// integers.  Plain C++ without a HIP header, so tests/sanitize/ks_san.cpp builds this file as it
-// stands (with planner.cpp) under ASan / UBSan.
+// integers.  The checks every limb-aware library makes are basis.cpp's; ks_validate keeps the
+// digit width's between their two steps.  Plain C++ without a HIP header, so
+// tests/sanitize/ks_san.cpp builds this file as it stands (with basis.cpp and planner.cpp) under
+// ASan / UBSan.
 #include "ks_plan.hpp"
 
 #include <string.h>
 
+#include "basis.hpp"
 #include "nttmul_ks.h"
 #include "planner.hpp"
 
 namespace nttmul {
 
-// In nttmul_galois_create's order: every EINVAL of either basis and of the digit width first, then
-// the unsupported shapes, then the word classes
+// In nttmul_galois_create's order (basis.hpp): every EINVAL of either basis and of the digit width
+// first, then the unsupported shapes, then the word classes
 int ks_validate(const nttmul_params *caller, size_t size, const uint64_t *q, uint32_t L,
                 const uint64_t *p, uint32_t K, uint32_t digit_limbs, KsPlan *P) {
-  if (!caller || size < NTTMUL_PARAMS_BASE_SIZE || size > sizeof(nttmul_params))
-    return NTTMUL_EINVAL;
-  nttmul_params prm;
-  memset(&prm, 0, sizeof(prm));
-  memcpy(&prm, caller, size);
-  if (!q || !p || L == 0 || L > NTTMUL_RNS_MAX_LIMBS || K == 0 || K > NTTMUL_RNS_MAX_LIMBS ||
-      prm.q || prm.psi)
-    return NTTMUL_EINVAL;
-  // a degree: a power of two from 256 up (above 65536 it is valid and unsupported, below)
-  const uint32_t n = prm.n;
-  if (n < 256 || n > (1u << 30) || (n & (n - 1))) return NTTMUL_EINVAL;
-  std::vector<uint64_t> all(q, q + L);
-  all.insert(all.end(), p, p + K);
-  for (size_t l = 0; l < all.size(); l++) {
-    const uint64_t m = all[l];
-    if (m < 3 || m >= (1ull << 62) || (m - 1) % (2ull * n) || !is_prime(m)) return NTTMUL_EINVAL;
-    for (size_t k = 0; k < l; k++)
-      if (all[k] == m) return NTTMUL_EINVAL;
-  }
+  const uint64_t *const bases[2] = {q, p};
+  const uint32_t limbs[2] = {L, K};
+  BasisRequest B;
+  // a degree above 65536 is valid and unsupported
+  if (const int st = basis_invalid(caller, size, bases, limbs, 2, 1u << 30, &B)) return st;
   // the extended basis is one nttmul_rns / nttmul_rnsmp context's
   if (digit_limbs == 0 || digit_limbs > L || L + K > NTTMUL_RNS_MAX_LIMBS) return NTTMUL_EINVAL;
-  if (n > 65536 || (prm.flags & NTTMUL_FLAG_CYCLIC)) return NTTMUL_EUNSUPPORTED;
-  const bool small = all[0] < (1ull << 31);
-  for (const uint64_t m : all) {
-    if (m >= (1ull << 31) && m < (1ull << 32)) return NTTMUL_EUNSUPPORTED;
-    if ((m < (1ull << 31)) != small) return NTTMUL_EUNSUPPORTED;
-    // (what nttmul_rns_create asks of a 32-bit basis at n = 4096)
-    if (small && n == 4096 && !p3_fold_ok(m)) return NTTMUL_EUNSUPPORTED;
-  }
-  P->n = n;
-  P->logn = (uint32_t)__builtin_ctz(n);
+  // (p3_fold: what nttmul_rns_create asks of a 32-bit basis at n = 4096)
+  if (const int st = basis_unsupported(&B, 256, 65536, true)) return st;
+  P->prm = B.prm;
+  P->n = B.prm.n;
+  P->logn = (uint32_t)__builtin_ctz(P->n);
   P->L = L;
   P->K = K;
   P->alpha = digit_limbs;
   P->dnum = (L + digit_limbs - 1) / digit_limbs;
-  P->flags = prm.flags;
-  P->word_bits = small ? 32 : 64;
+  P->flags = B.prm.flags;
+  P->word_bits = B.word_bits;
   P->q.assign(q, q + L);
   P->p.assign(p, p + K);
   return NTTMUL_OK;

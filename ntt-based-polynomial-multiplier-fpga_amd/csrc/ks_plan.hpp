@@ -15,6 +15,7 @@ namespace nttmul {
 struct KsPlan {
   uint32_t n = 0, logn = 0, L = 0, K = 0, alpha = 0, dnum = 0, flags = 0;
   int word_bits = 0;
+  nttmul_params prm = {};               // the caller's params, zero-extended (create: the devices)
   std::vector<uint64_t> q, p;           // Q [L], P [K]
   std::vector<uint64_t> inv, w, gadget; // [L], [L][L + K], [dnum][L + K]
   std::vector<uint64_t> pinv, pw, Pinv; // [K], [K][L], [L]: the converter from = P, to = Q

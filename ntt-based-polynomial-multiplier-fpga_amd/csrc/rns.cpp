@@ -3,15 +3,17 @@
 // operands (rns.hip).  It plans each limb with the planner of the plain contexts (planner.hpp) and
 // keeps, per device, the limbs' twiddle tables and one table of kernel constants per kernel family
 // (rns.hpp).  No resident server, no issue-priority rule, no CPU fallback.
+// The create-time checks are basis.cpp's and the context runtime (devices, error text, the device
+// and host forms of a call) limb_ctx.cpp's.  This file keeps its handle, its run, and the pieces
+// rnsmp.cpp takes from it (rns.hpp): the limbs' tables and their upload, op_args and op_words.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <string.h>
 
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "basis.hpp"
+#include "limb_ctx.hpp"
 #include "nttmul_rns.h"
 #include "planner.hpp"
 #include "rns.hpp"
@@ -20,15 +22,10 @@ using namespace nttmul;
 
 namespace {
 
-constexpr int kMaxDev = 16;
-
 struct RnsDev {
-  int id = -1;
-  hipStream_t stream = nullptr;               // the host forms' stream
+  LimbDev base;
   void *tw = nullptr;                         // fw, iw of limb 0, fw, iw of limb 1, ...
   void *tab[kRnsFamilies] = {nullptr, nullptr, nullptr};
-  uint64_t *q = nullptr;
-  int *flag = nullptr;                        // range-check result
 };
 
 }  // namespace
@@ -38,37 +35,10 @@ struct nttmul_rns {
   int word_bits = 0, ndev = 0;
   std::vector<Plan> plan;                     // per limb (twiddle vectors released after upload)
   RnsDev dev[kMaxDev];
-  char err[256] = {0};
+  char err[kErrBytes] = {0};
 };
 
-namespace {
-
-struct DeviceGuard {  // restores the caller's current device on scope exit
-  int prev = -1;
-  DeviceGuard() { (void)hipGetDevice(&prev); }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-std::mutex g_err_mu;
-
-int fail(nttmul_rns *r, hipError_t e, const char *what) {
-  std::lock_guard<std::mutex> l(g_err_mu);
-  snprintf(r->err, sizeof(r->err), "%s: %s", what, hipGetErrorString(e));
-  return e == hipErrorOutOfMemory ? NTTMUL_ENOMEM : NTTMUL_EHIP;
-}
-
-void set_err(nttmul_rns *r, const char *msg) {
-  std::lock_guard<std::mutex> l(g_err_mu);
-  snprintf(r->err, sizeof(r->err), "%s", msg);
-}
-
-#define RNS_TRY(r, expr)                             \
-  do {                                               \
-    hipError_t _e = (expr);                          \
-    if (_e != hipSuccess) return fail(r, _e, #expr); \
-  } while (0)
+namespace nttmul {
 
 LaunchTables limb_tables(const Plan &P, const void *fw, const void *iw) {
   LaunchTables T;
@@ -87,137 +57,111 @@ LaunchTables limb_tables(const Plan &P, const void *fw, const void *iw) {
   return T;
 }
 
-RnsTables tables_for(const nttmul_rns *r, const RnsDev &d) {
+RnsTables tables_for(uint32_t logn, uint32_t limbs, int word_bits, const void *tw,
+                     void *const tab[kRnsFamilies], const uint64_t *q) {
   RnsTables T;
-  T.logn = r->logn;
-  T.limbs = r->limbs;
-  T.word_bits = r->word_bits;
-  for (int f = 0; f < kRnsFamilies; f++) T.tab[f] = d.tab[f];
-  T.tw = d.tw;
-  T.q = d.q;
+  T.logn = logn;
+  T.limbs = limbs;
+  T.word_bits = word_bits;
+  for (int f = 0; f < kRnsFamilies; f++) T.tab[f] = tab[f];
+  T.tw = tw;
+  T.q = q;
   return T;
 }
 
-RnsDev *find_dev(nttmul_rns *r, int dev) {
-  for (int i = 0; i < r->ndev; i++)
-    if (r->dev[i].id == dev) return &r->dev[i];
-  return nullptr;
-}
-
-// One device's tables: the limbs' twiddles in one allocation, then the three KParams tables built
-// from pointers into it
-int setup_device(nttmul_rns *r, RnsDev &d) {
-  const size_t tbytes = r->plan[0].fw.size(), ebytes = rns_entry_bytes(r->word_bits);
-  const uint32_t L = r->limbs;
-  RNS_TRY(r, hipSetDevice(d.id));
-  RNS_TRY(r, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-  RNS_TRY(r, hipMalloc(&d.tw, 2 * tbytes * L));
-  RNS_TRY(r, hipMalloc((void **)&d.q, sizeof(uint64_t) * L));
-  RNS_TRY(r, hipMalloc((void **)&d.flag, sizeof(int)));
+int upload_limb_tables(char *err, const std::vector<Plan> &plan, int word_bits, LimbDev &d,
+                       void **tw, void *tab[kRnsFamilies],
+                       hipError_t (*fill)(const LaunchTables &, int, void *)) {
+  const size_t tbytes = plan[0].fw.size(), ebytes = rns_entry_bytes(word_bits);
+  const uint32_t L = (uint32_t)plan.size();
+  LIMB_TRY(err, hipSetDevice(d.id));
+  LIMB_TRY(err, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+  LIMB_TRY(err, hipMalloc(tw, 2 * tbytes * L));
+  LIMB_TRY(err, hipMalloc((void **)&d.q, sizeof(uint64_t) * L));
+  LIMB_TRY(err, hipMalloc((void **)&d.flag, sizeof(int)));
   std::vector<uint64_t> q(L);
   std::vector<uint8_t> host(ebytes * L);
   for (uint32_t l = 0; l < L; l++) {
-    char *fw = (char *)d.tw + 2 * tbytes * l;
-    RNS_TRY(r, hipMemcpy(fw, r->plan[l].fw.data(), tbytes, hipMemcpyHostToDevice));
-    RNS_TRY(r, hipMemcpy(fw + tbytes, r->plan[l].iw.data(), tbytes, hipMemcpyHostToDevice));
-    q[l] = r->plan[l].q;
+    char *fw = (char *)*tw + 2 * tbytes * l;
+    LIMB_TRY(err, hipMemcpy(fw, plan[l].fw.data(), tbytes, hipMemcpyHostToDevice));
+    LIMB_TRY(err, hipMemcpy(fw + tbytes, plan[l].iw.data(), tbytes, hipMemcpyHostToDevice));
+    q[l] = plan[l].q;
   }
-  RNS_TRY(r, hipMemcpy(d.q, q.data(), sizeof(uint64_t) * L, hipMemcpyHostToDevice));
+  LIMB_TRY(err, hipMemcpy(d.q, q.data(), sizeof(uint64_t) * L, hipMemcpyHostToDevice));
   for (int f = 0; f < kRnsFamilies; f++) {
     for (uint32_t l = 0; l < L; l++) {
-      const char *fw = (const char *)d.tw + 2 * tbytes * l;
-      RNS_TRY(r, rns_fill_entry(limb_tables(r->plan[l], fw, fw + tbytes), f,
-                                host.data() + ebytes * l));
+      const char *fw = (const char *)*tw + 2 * tbytes * l;
+      LIMB_TRY(err, fill(limb_tables(plan[l], fw, fw + tbytes), f, host.data() + ebytes * l));
     }
-    RNS_TRY(r, hipMalloc(&d.tab[f], ebytes * L));
-    RNS_TRY(r, hipMemcpy(d.tab[f], host.data(), ebytes * L, hipMemcpyHostToDevice));
+    LIMB_TRY(err, hipMalloc(&tab[f], ebytes * L));
+    LIMB_TRY(err, hipMemcpy(tab[f], host.data(), ebytes * L, hipMemcpyHostToDevice));
   }
   return NTTMUL_OK;
 }
 
-// what is decided before any device access
-int op_args(const nttmul_rns *r, int op, const void *c, const void *a, const void *b, size_t batch,
+int op_args(bool have_ctx, int op, const void *c, const void *a, const void *b, size_t batch,
             uint32_t terms) {
-  if (!r || (op == kRnsMac && !terms)) return NTTMUL_EINVAL;
+  if (!have_ctx || (op == kRnsMac && !terms)) return NTTMUL_EINVAL;
   const bool two = op == kRnsMultiply || op == kRnsMac;
   if (batch && (!c || !a || (two && !b))) return NTTMUL_EINVAL;
   return NTTMUL_OK;
 }
 
-// words of the operands of one call: c, a, b (b 0 for the transforms)
-void op_words(const nttmul_rns *r, int op, size_t batch, uint32_t terms, int shared,
+void op_words(uint32_t limbs, uint32_t n, int op, size_t batch, uint32_t terms, int shared,
               size_t words[3]) {
-  const size_t poly = (size_t)r->limbs * r->n;
+  const size_t poly = (size_t)limbs * n;
   words[0] = batch * poly;
   words[1] = op == kRnsMac ? batch * terms * poly : batch * poly;
   words[2] = op == kRnsMac ? (shared ? 1 : batch) * terms * poly
                            : op == kRnsMultiply ? batch * poly : 0;
 }
 
+}  // namespace nttmul
+
+namespace {
+
+RnsTables view(const nttmul_rns *r, const RnsDev &d) {
+  return tables_for(r->logn, r->limbs, r->word_bits, d.tw, d.tab, d.base.q);
+}
+
 // on d (the current device), stream s
 int run(nttmul_rns *r, RnsDev &d, int op, void *c, const void *a, const void *b, size_t batch,
         uint32_t terms, int shared, hipStream_t s) {
   if (!batch) return NTTMUL_OK;
-  const RnsTables T = tables_for(r, d);
   if (r->flags & NTTMUL_FLAG_VALIDATE) {
     size_t words[3];
-    op_words(r, op, batch, terms, shared, words);
-    RNS_TRY(r, hipMemsetAsync(d.flag, 0, sizeof(int), s));
-    RNS_TRY(r, launch_rns_check(T, a, words[1], d.flag, s));
-    if (words[2]) RNS_TRY(r, launch_rns_check(T, b, words[2], d.flag, s));
-    int bad = 0;
-    RNS_TRY(r, hipMemcpyAsync(&bad, d.flag, sizeof(int), hipMemcpyDeviceToHost, s));
-    RNS_TRY(r, hipStreamSynchronize(s));
-    if (bad) {
-      set_err(r, "input coefficient >= its limb's modulus");
-      return NTTMUL_ERANGE;
-    }
+    op_words(r->limbs, r->n, op, batch, terms, shared, words);
+    if (const int st = check_range(r->err, d.base.flag, d.base.q, r->limbs, r->logn, r->word_bits,
+                                   a, words[1], b, words[2],
+                                   "input coefficient >= its limb's modulus", s))
+      return st;
   }
-  RNS_TRY(r, launch_rns(T, op, c, a, b, batch, terms, shared, s));
+  LIMB_TRY(r->err, launch_rns(view(r, d), op, c, a, b, batch, terms, shared, s));
   return NTTMUL_OK;
 }
 
 int device_op(nttmul_rns *r, int op, void *c, const void *a, const void *b, size_t batch,
               uint32_t terms, int shared, int dev, void *stream) {
-  if (const int st = op_args(r, op, c, a, b, batch, terms)) return st;
-  RnsDev *d = find_dev(r, dev);
-  if (!d) return NTTMUL_ENODEV;
-  DeviceGuard guard;
-  RNS_TRY(r, hipSetDevice(d->id));
-  return run(r, *d, op, c, a, b, batch, terms, shared, (hipStream_t)stream);
+  if (const int st = op_args(r != nullptr, op, c, a, b, batch, terms)) return st;
+  return on_device(r->err, r->dev, r->ndev, dev, [&](RnsDev &d) {
+    return run(r, d, op, c, a, b, batch, terms, shared, (hipStream_t)stream);
+  });
 }
 
 // Host buffers: dev[0], device buffers owned by the call, the device path, copy back, synchronise
 int host_op(nttmul_rns *r, int op, void *c, const void *a, const void *b, size_t batch,
             uint32_t terms, int shared) {
-  if (const int st = op_args(r, op, c, a, b, batch, terms)) return st;
+  if (const int st = op_args(r != nullptr, op, c, a, b, batch, terms)) return st;
   if (!batch) return NTTMUL_OK;
   RnsDev &d = r->dev[0];
-  DeviceGuard guard;
-  RNS_TRY(r, hipSetDevice(d.id));
   size_t words[3];
-  op_words(r, op, batch, terms, shared, words);
+  op_words(r->limbs, r->n, op, batch, terms, shared, words);
   const size_t wb = (size_t)r->word_bits / 8;
-  const void *src[3] = {nullptr, a, b};
-  void *buf[3] = {nullptr, nullptr, nullptr};  // c, a, b
-  int st = NTTMUL_OK;
-  const auto step = [&](hipError_t e, const char *what) {
-    if (!st && e != hipSuccess) st = fail(r, e, what);
-    return !st;
-  };
-  for (int i = 0; i < 3 && !st; i++)
-    if (words[i]) step(hipMalloc(&buf[i], words[i] * wb), "rns host buffers");
-  for (int i = 1; i < 3 && !st; i++)
-    if (words[i])
-      step(hipMemcpyAsync(buf[i], src[i], words[i] * wb, hipMemcpyHostToDevice, d.stream),
-           "rns copy in");
-  if (!st) st = run(r, d, op, buf[0], buf[1], buf[2], batch, terms, shared, d.stream);
-  if (!st) step(hipMemcpyAsync(c, buf[0], words[0] * wb, hipMemcpyDeviceToHost, d.stream), "rns copy out");
-  // (also after a failure: nothing of this call may still run when its buffers go)
-  step(hipStreamSynchronize(d.stream), "rns synchronise");
-  for (void *p : buf)
-    if (p) (void)hipFree(p);
-  return st;
+  const Staged ops[3] = {{nullptr, c, words[0] * wb}, {a, nullptr, words[1] * wb},
+                         {b, nullptr, words[2] * wb}};
+  return staged_op(r->err, d.base, "rns", ops, 3, [&](void *const *buf) {
+    return run(r, d, op, buf[0], buf[1], buf[2], batch, terms, shared, d.base.stream);
+  });
 }
 
 }  // namespace
@@ -228,68 +172,40 @@ int nttmul_rns_create(nttmul_rns **out, const nttmul_params *caller, size_t size
                       const uint64_t *q, uint32_t limbs) {
   if (!out) return NTTMUL_EINVAL;
   *out = nullptr;
-  if (!caller || size < NTTMUL_PARAMS_BASE_SIZE || size > sizeof(nttmul_params))
-    return NTTMUL_EINVAL;
-  nttmul_params p;
-  memset(&p, 0, sizeof(p));
-  memcpy(&p, caller, size);
-  if (!q || limbs == 0 || limbs > NTTMUL_RNS_MAX_LIMBS || p.q || p.psi) return NTTMUL_EINVAL;
-  // what nttmul_create refuses (planner.cpp make_plan; psi = 0 always finds a root then)
-  const uint32_t n = p.n;
-  if (n < 256 || n > 65536 || (n & (n - 1))) return NTTMUL_EINVAL;
-  for (uint32_t l = 0; l < limbs; l++) {
-    if (q[l] < 3 || q[l] >= (1ull << 62) || (q[l] - 1) % (2ull * n) || !is_prime(q[l]))
-      return NTTMUL_EINVAL;
-    for (uint32_t m = 0; m < l; m++)
-      if (q[m] == q[l]) return NTTMUL_EINVAL;
-  }
-  if (n > 4096 || (p.flags & NTTMUL_FLAG_CYCLIC)) return NTTMUL_EUNSUPPORTED;
-  // one word class per context: every q_l < 2^31 (32-bit words) or every q_l >= 2^32 (64-bit)
-  const bool small = q[0] < (1ull << 31);
-  for (uint32_t l = 0; l < limbs; l++) {
-    if (q[l] >= (1ull << 31) && q[l] < (1ull << 32)) return NTTMUL_EUNSUPPORTED;
-    if ((q[l] < (1ull << 31)) != small) return NTTMUL_EUNSUPPORTED;
-    // Arith32P3's fold at n = 4096: holds for every q < 2^31, kept as a checked assumption
-    if (small && n == 4096 && !p3_fold_ok(q[l])) return NTTMUL_EUNSUPPORTED;
-  }
+  BasisRequest B;
+  if (const int st = basis_invalid(caller, size, &q, &limbs, 1, 65536, &B)) return st;
+  if (const int st = basis_unsupported(&B, 256, 4096, true)) return st;
   nttmul_rns *r = new (std::nothrow) nttmul_rns();
   if (!r) return NTTMUL_ENOMEM;
-  r->n = n;
+  r->n = B.prm.n;
   r->limbs = limbs;
-  r->flags = p.flags;
-  r->word_bits = small ? 32 : 64;
+  r->flags = B.prm.flags;
+  r->word_bits = B.word_bits;
   r->plan.resize(limbs);
   for (uint32_t l = 0; l < limbs; l++) {
-    const int st = make_plan(n, q[l], 0, &r->plan[l], false);
+    const int st = make_plan(r->n, q[l], 0, &r->plan[l], false);
     if (st) {
       delete r;
       return st;
     }
   }
   r->logn = r->plan[0].logn;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-    (void)hipGetLastError();
+  DevRange R;
+  if (const int st = select_devices(B.prm, &R)) {
     delete r;
-    return NTTMUL_ENODEV;
-  }
-  const int first = p.first_dev < 0 ? 0 : p.first_dev;
-  const int ndev = p.ndev <= 0 ? count - first : p.ndev;
-  const bool share = (p.flags & NTTMUL_FLAG_SHARE_DEVICES) != 0;
-  if (first >= count || ndev <= 0 || (!share && first + ndev > count) || ndev > kMaxDev) {
-    delete r;
-    return NTTMUL_ENODEV;
+    return st;
   }
   DeviceGuard guard;
-  for (int i = 0; i < ndev; i++) {
+  for (int i = 0; i < R.ndev; i++) {
     RnsDev &d = r->dev[i];
-    d.id = first + i % (count - first);
+    d.base.id = R.id(i);
     r->ndev = i + 1;
-    const int st = setup_device(r, d);
+    const int st =
+        upload_limb_tables(r->err, r->plan, r->word_bits, d.base, &d.tw, d.tab, rns_fill_entry);
     if (st) {
-      fprintf(stderr, "nttmul_rns: %s\n", r->err);
+      const int ret = create_failed("nttmul_rns", r->err, st);
       nttmul_rns_destroy(r);
-      return st == NTTMUL_EHIP ? NTTMUL_ENODEV : st;
+      return ret;
     }
   }
   for (Plan &P : r->plan) {  // the devices hold the tables now
@@ -302,16 +218,9 @@ int nttmul_rns_create(nttmul_rns **out, const nttmul_params *caller, size_t size
 
 void nttmul_rns_destroy(nttmul_rns *r) {
   if (!r) return;
-  DeviceGuard guard;
-  for (int i = 0; i < r->ndev; i++) {
-    RnsDev &d = r->dev[i];
-    if (d.id < 0) continue;
-    (void)hipSetDevice(d.id);
-    if (d.stream) (void)hipStreamSynchronize(d.stream);
-    for (void *p : {d.tw, d.tab[0], d.tab[1], d.tab[2], (void *)d.q, (void *)d.flag})
-      if (p) (void)hipFree(p);
-    if (d.stream) (void)hipStreamDestroy(d.stream);
-  }
+  destroy_devices(r->dev, r->ndev, [](RnsDev &d) {
+    free_each({d.tw, d.tab[0], d.tab[1], d.tab[2], d.base.q, d.base.flag});
+  });
   delete r;
 }
 
@@ -329,19 +238,7 @@ int nttmul_rns_get_info(const nttmul_rns *r, nttmul_rns_info *info) {
 
 int nttmul_rns_limb_info(const nttmul_rns *r, uint32_t limb, nttmul_info *info) {
   if (!r || !info || limb >= r->limbs) return NTTMUL_EINVAL;
-  const Plan &P = r->plan[limb];
-  info->n = P.n;
-  info->logn = P.logn;
-  info->q = P.q;
-  info->psi = P.psi;
-  info->omega = P.omega;
-  info->inv_psi = P.inv_psi;
-  info->inv_omega = P.inv_omega;
-  info->inv_n = P.inv_n;
-  info->word_bits = (uint32_t)P.word_bits;
-  info->ndev = r->ndev;
-  info->kernel = 1;
-  info->cyclic = 0;
+  fill_info(r->plan[limb], r->ndev, 1, info);
   return NTTMUL_OK;
 }
 
@@ -379,13 +276,8 @@ int nttmul_rns_mac_ntt(nttmul_rns *r, void *c, const void *a, const void *b_hat,
 int nttmul_rns_kernel_name(const nttmul_rns *r, int op, char *buf, size_t cap) {
   if (!r || op < kRnsMultiply || op > kRnsMac || (cap && !buf)) return NTTMUL_EINVAL;
   std::string name;
-  if (describe_rns(tables_for(r, r->dev[0]), op, &name) != hipSuccess) return NTTMUL_EUNSUPPORTED;
-  if (cap) {
-    const size_t k = name.size() < cap - 1 ? name.size() : cap - 1;
-    memcpy(buf, name.data(), k);
-    buf[k] = 0;
-  }
-  return (int)name.size();
+  if (describe_rns(view(r, r->dev[0]), op, &name) != hipSuccess) return NTTMUL_EUNSUPPORTED;
+  return copy_name(name, buf, cap);
 }
 
 }  // extern "C"

@@ -1,6 +1,9 @@
 // rns.hpp — internal interface between the host entry points of include/nttmul_rns.h (rns.cpp)
-// and the launchers of rns.hip.  lib/libnttmul_rns.so only.
+// and the launchers of rns.hip, and the host pieces rns.cpp shares with rnsmp.cpp.
+// lib/libnttmul_rns.so only.
 #pragma once
+#include <vector>
+
 #include "launch.hpp"
 
 namespace nttmul {
@@ -43,5 +46,28 @@ hipError_t describe_rns(const RnsTables &T, int op, std::string *out);
 // *bad |= 1 when a word i < total of a is >= q[(i / n) mod limbs]
 hipError_t launch_rns_check(const RnsTables &T, const void *a, size_t total, int *bad,
                             hipStream_t s);
+
+// ---- host side, shared by rns.cpp (which defines it) and rnsmp.cpp ------------------------------
+
+struct Plan;     // planner.hpp
+struct LimbDev;  // limb_ctx.hpp
+
+// One limb's LaunchTables from its plan; fw / iw: the limb's device twiddle tables
+LaunchTables limb_tables(const Plan &P, const void *fw, const void *iw);
+// The view of one device of a context, from the fields both contexts keep
+RnsTables tables_for(uint32_t logn, uint32_t limbs, int word_bits, const void *tw,
+                     void *const tab[kRnsFamilies], const uint64_t *q);
+// What a call decides before any device access (have_ctx: the handle is not NULL)
+int op_args(bool have_ctx, int op, const void *c, const void *a, const void *b, size_t batch,
+            uint32_t terms);
+// words of the operands of one call: c, a, b (b 0 for the transforms)
+void op_words(uint32_t limbs, uint32_t n, int op, size_t batch, uint32_t terms, int shared,
+              size_t words[3]);
+// One device's stream, moduli, flag and tables at create: the limbs' twiddles in one allocation
+// *tw (fw, iw of limb 0, fw, iw of limb 1, ...), then the three KParams tables tab[] that `fill`
+// (rns_fill_entry or rnsmp_fill_entry) builds from pointers into it
+int upload_limb_tables(char *err, const std::vector<Plan> &plan, int word_bits, LimbDev &d,
+                       void **tw, void *tab[kRnsFamilies],
+                       hipError_t (*fill)(const LaunchTables &, int, void *));
 
 }  // namespace nttmul

@@ -728,95 +728,84 @@ class MacContext(Context):
         return c
 
 
-# ---- one launch over all limbs of an RNS basis (include/nttmul_rns.h) ----------------------------
+# ---- what the limb-aware libraries' bindings share ------------------------------------------------
 
-RNS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_rns.so")
-RNS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_rns.h")
-RNS_MAX_LIMBS = 64
-RNS_OPS = ("multiply", "forward", "inverse", "mac")   # nttmul_rns_kernel_name's op numbers
-
-_RNS_LIB: Optional[ctypes.CDLL] = None
+_LIMB_LIBS: dict = {}
 
 
-class RnsInfo(ctypes.Structure):
-    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("limbs", ctypes.c_uint32),
-                ("word_bits", ctypes.c_uint32), ("ndev", ctypes.c_int)]
-
-
-def load_rns_library() -> ctypes.CDLL:
-    """Load lib/libnttmul_rns.so (include/nttmul_rns.h): the ABI and kernels of libnttmul_mac.so
-    plus the limb-aware kernels.  load_library() and load_mac_library() are unaffected."""
-    global _RNS_LIB
-    if _RNS_LIB is not None:
-        return _RNS_LIB
-    if not os.path.exists(RNS_LIB_PATH):
-        raise ImportError(f"{RNS_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
-    _RNS_LIB = _bind_rns(_bind_mac(_bind(ctypes.CDLL(RNS_LIB_PATH))))
-    return _RNS_LIB
-
-
-def _bind_rns(lib: ctypes.CDLL) -> ctypes.CDLL:
-    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-    lib.nttmul_rns_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(_Params), sz,
-                                      ctypes.POINTER(ctypes.c_uint64), u32]
-    lib.nttmul_rns_destroy.argtypes = [vp]
-    lib.nttmul_rns_destroy.restype = None
-    lib.nttmul_rns_last_error.argtypes = [vp]
-    lib.nttmul_rns_last_error.restype = ctypes.c_char_p
-    lib.nttmul_rns_get_info.argtypes = [vp, ctypes.POINTER(RnsInfo)]
-    lib.nttmul_rns_limb_info.argtypes = [vp, u32, ctypes.POINTER(Info)]
-    lib.nttmul_rns_multiply_device.argtypes = [vp, vp, vp, vp, sz, i32, vp]
-    lib.nttmul_rns_forward_device.argtypes = [vp, vp, vp, sz, i32, vp]
-    lib.nttmul_rns_inverse_device.argtypes = [vp, vp, vp, sz, i32, vp]
-    lib.nttmul_rns_mac_ntt_device.argtypes = [vp, vp, vp, vp, sz, u32, i32, i32, vp]
-    lib.nttmul_rns_multiply.argtypes = [vp, vp, vp, vp, sz]
-    lib.nttmul_rns_forward.argtypes = [vp, vp, vp, sz]
-    lib.nttmul_rns_inverse.argtypes = [vp, vp, vp, sz]
-    lib.nttmul_rns_mac_ntt.argtypes = [vp, vp, vp, vp, sz, u32, i32]
-    lib.nttmul_rns_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
+def _load_limb_library(path: str, *binders) -> ctypes.CDLL:
+    """The library at `path`, loaded once: the plain and the mac ABI bound, then each of
+    `binders` applied."""
+    lib = _LIMB_LIBS.get(path)
+    if lib is None:
+        if not os.path.exists(path):
+            raise ImportError(f"{path} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
+        lib = _bind_mac(_bind(ctypes.CDLL(path)))
+        for bind in binders:
+            bind(lib)
+        _LIMB_LIBS[path] = lib
     return lib
 
 
-def rns_exported_symbols() -> list:
-    """Function names declared in include/nttmul_rns.h."""
+def _header_symbols(header: str, prefix: str) -> list:
+    """Function names starting with `prefix` declared in the header at `header`."""
     import re
-    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_rns_\w+)\s*\(",
-                                 open(RNS_HEADER_PATH).read(), re.M)))
+    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(%s\w+)\s*\(" % prefix,
+                                 open(header).read(), re.M)))
 
 
-class RnsContext:
-    """nttmul_rns: the moduli q_0 .. q_{L-1} of one degree n <= 4096, every operation one launch
-    over [batch, limbs, n] operands (include/nttmul_rns.h).  Words are info.word_bits wide: 32
-    when every q_l < 2^31, 64 when every q_l >= 2^32.
+def _flags(validate: bool, cyclic: bool, share_devices: bool) -> int:
+    return ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
+            | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
 
-    Caller memory, as for Context: operands need the alignment of their word only; out may be the
-    input itself for forward and inverse, c must not overlap a, b or b_hat, and partial overlap is
-    never allowed; a call writes exactly batch * limbs * n words of its output and nothing else
-    in caller memory, and never writes an input."""
 
-    def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
-                 cyclic: bool = False, share_devices: bool = False):
-        self._lib = load_rns_library()
+def _bind_handle(lib: ctypes.CDLL, prefix: str, info, create_args: list) -> None:
+    """The entry points every handle has: create (after out, params and size: create_args),
+    destroy, last_error, get_info."""
+    vp = ctypes.c_void_p
+    getattr(lib, f"{prefix}_create").argtypes = [ctypes.POINTER(vp), ctypes.POINTER(_Params),
+                                                 ctypes.c_size_t] + create_args
+    getattr(lib, f"{prefix}_destroy").argtypes = [vp]
+    getattr(lib, f"{prefix}_destroy").restype = None
+    getattr(lib, f"{prefix}_last_error").argtypes = [vp]
+    getattr(lib, f"{prefix}_last_error").restype = ctypes.c_char_p
+    getattr(lib, f"{prefix}_get_info").argtypes = [vp, ctypes.POINTER(info)]
+
+
+class _Entries:
+    """lib.<prefix>_<name> as the attribute <name>: looked up on first use, a plain attribute from
+    then on, so a call costs what `lib.<prefix>_<name>` written out costs."""
+
+    def __init__(self, lib: ctypes.CDLL, prefix: str):
+        self._lib, self._prefix = lib, prefix
+
+    def __getattr__(self, name: str):
+        fn = getattr(self._lib, f"{self._prefix}_{name}")
+        setattr(self, name, fn)
+        return fn
+
+
+class _Handle:
+    """What the handle classes of the limb-aware libraries share.  Class attributes: _PREFIX, the
+    C prefix of the library's entry points (self._c.<name> is <prefix>_<name>); _OPS, the op names
+    in <prefix>_kernel_name's numbering; _NAME_CAP, the bytes kernel_name asks for."""
+    _PREFIX = ""
+    _OPS: tuple = ()
+    _NAME_CAP = 256
+
+    def _open(self, lib: ctypes.CDLL, info, prm: _Params, *args):
+        """<prefix>_create(&h, &prm, sizeof prm, *args), then <prefix>_get_info into self.info."""
+        self._lib, self._c = lib, _Entries(lib, self._PREFIX)
         self._h = ctypes.c_void_p()
-        moduli = [int(q) for q in moduli]
-        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
-                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
-        prm = _Params(n, 0, 0, ndev, first_dev, flags, 0, 0, 0, 0, 0)
-        qs = (ctypes.c_uint64 * max(1, len(moduli)))(*moduli)
-        st = self._lib.nttmul_rns_create(ctypes.byref(self._h), ctypes.byref(prm),
-                                         ctypes.sizeof(prm), qs, len(moduli))
+        st = self._c.create(ctypes.byref(self._h), ctypes.byref(prm), ctypes.sizeof(prm), *args)
         if st != NTTMUL_OK:
-            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
-        info = RnsInfo()
-        self._lib.nttmul_rns_get_info(self._h, ctypes.byref(info))
+            raise NttmulError(st, lib.nttmul_strerror(st).decode())
+        self._c.get_info(self._h, ctypes.byref(info))
         self.info = info
-        self.n, self.limbs, self.word_bits = info.n, info.limbs, info.word_bits
-        self.moduli = tuple(moduli)
-        self.first_dev = first_dev
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            self._lib.nttmul_rns_destroy(self._h)
+            self._c.destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -834,49 +823,108 @@ class RnsContext:
     def _check(self, st: int):
         if st != NTTMUL_OK:
             raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
-                                  f"{self._lib.nttmul_rns_last_error(self._h).decode()}")
+                                  f"{self._c.last_error(self._h).decode()}")
 
     @property
     def io_dtype(self):
         return np.uint32 if self.word_bits == 32 else np.uint64
 
-    def limb_info(self, limb: int) -> Info:
-        """nttmul_rns_limb_info: q, psi, omega, ... of one limb."""
-        info = Info()
-        self._check(self._lib.nttmul_rns_limb_info(self._h, limb, ctypes.byref(info)))
-        return info
-
-    def kernel_name(self, op) -> str:
-        """nttmul_rns_kernel_name for op 0..3 or "multiply" / "forward" / "inverse" / "mac", e.g.
-        "k_rns_rows<Arith32P3,u32,12>"."""
-        op = RNS_OPS.index(op) if isinstance(op, str) else int(op)
-        buf = ctypes.create_string_buffer(256)
-        st = self._lib.nttmul_rns_kernel_name(self._h, op, buf, len(buf))
+    def _kernel_name(self, op, *extra) -> str:
+        op = self._OPS.index(op) if isinstance(op, str) else int(op)
+        buf = ctypes.create_string_buffer(self._NAME_CAP)
+        st = self._c.kernel_name(self._h, op, *extra, buf, len(buf))
         if st < 0:
             self._check(st)
         return buf.value.decode()
 
-    # device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`
+
+class _LimbContext(_Handle):
+    """A handle over one basis `moduli` and [batch, limbs, n] operands (RnsContext, RnsMpContext,
+    GaloisContext): n, limbs, word_bits, moduli, first_dev, and <prefix>_limb_info."""
+
+    def _open_limbs(self, lib, info, n, moduli, ndev, first_dev, flags, scratch_mb=0):
+        moduli = [int(q) for q in moduli]
+        prm = _Params(n, 0, 0, ndev, first_dev, flags, 0, 0, 0, scratch_mb, 0)
+        qs = (ctypes.c_uint64 * max(1, len(moduli)))(*moduli)
+        self._open(lib, info, prm, qs, len(moduli))
+        self.n, self.limbs, self.word_bits = info.n, info.limbs, info.word_bits
+        self.moduli = tuple(moduli)
+        self.first_dev = first_dev
+
+    def limb_info(self, limb: int) -> Info:
+        """<prefix>_limb_info: q, psi, omega, ... of one limb."""
+        info = Info()
+        self._check(self._c.limb_info(self._h, limb, ctypes.byref(info)))
+        return info
 
     def _dev_args(self, operands, polys, dev):
         return [_dev_arg(t, k * self.limbs, self.n, self.word_bits, dev)
                 for t, k in zip(operands, polys)]
 
+
+# ---- one launch over all limbs of an RNS basis (include/nttmul_rns.h) ----------------------------
+
+RNS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_rns.so")
+RNS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_rns.h")
+RNS_MAX_LIMBS = 64
+RNS_OPS = ("multiply", "forward", "inverse", "mac")   # nttmul_rns_kernel_name's op numbers
+
+
+class RnsInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("limbs", ctypes.c_uint32),
+                ("word_bits", ctypes.c_uint32), ("ndev", ctypes.c_int)]
+
+
+def load_rns_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_rns.so (include/nttmul_rns.h): the ABI and kernels of libnttmul_mac.so
+    plus the limb-aware kernels.  load_library() and load_mac_library() are unaffected."""
+    return _load_limb_library(RNS_LIB_PATH, _bind_rns)
+
+
+def _bind_rns(lib: ctypes.CDLL, prefix: str = "nttmul_rns", info=RnsInfo) -> ctypes.CDLL:
+    """nttmul_rns_*, and with the other prefix and info type nttmul_rnsmp_*."""
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    _bind_handle(lib, prefix, info, [ctypes.POINTER(ctypes.c_uint64), u32])
+    getattr(lib, f"{prefix}_limb_info").argtypes = [vp, u32, ctypes.POINTER(Info)]
+    getattr(lib, f"{prefix}_multiply_device").argtypes = [vp, vp, vp, vp, sz, i32, vp]
+    getattr(lib, f"{prefix}_forward_device").argtypes = [vp, vp, vp, sz, i32, vp]
+    getattr(lib, f"{prefix}_inverse_device").argtypes = [vp, vp, vp, sz, i32, vp]
+    getattr(lib, f"{prefix}_mac_ntt_device").argtypes = [vp, vp, vp, vp, sz, u32, i32, i32, vp]
+    getattr(lib, f"{prefix}_multiply").argtypes = [vp, vp, vp, vp, sz]
+    getattr(lib, f"{prefix}_forward").argtypes = [vp, vp, vp, sz]
+    getattr(lib, f"{prefix}_inverse").argtypes = [vp, vp, vp, sz]
+    getattr(lib, f"{prefix}_mac_ntt").argtypes = [vp, vp, vp, vp, sz, u32, i32]
+    getattr(lib, f"{prefix}_kernel_name").argtypes = [vp, i32, ctypes.c_char_p, sz]
+    return lib
+
+
+def rns_exported_symbols() -> list:
+    """Function names declared in include/nttmul_rns.h."""
+    return _header_symbols(RNS_HEADER_PATH, "nttmul_rns_")
+
+
+class _RnsOps(_LimbContext):
+    """What RnsContext and RnsMpContext share: the four operations over [batch, limbs, n]
+    operands, as <prefix>_<op> on host arrays and <prefix>_<op>_device on device memory."""
+    _OPS = RNS_OPS
+
+    # device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`
+
     def multiply_device(self, c, a, b, batch: int, dev: Optional[int] = None, stream: int = 0):
         """c, a, b: [batch][limbs][n]."""
         dev = self.first_dev if dev is None else dev
         args = self._dev_args((c, a, b), (batch,) * 3, dev)
-        self._check(self._lib.nttmul_rns_multiply_device(self._h, *args, batch, dev, stream or None))
+        self._check(self._c.multiply_device(self._h, *args, batch, dev, stream or None))
 
     def forward_device(self, out, a, batch: int, dev: Optional[int] = None, stream: int = 0):
         dev = self.first_dev if dev is None else dev
         args = self._dev_args((out, a), (batch,) * 2, dev)
-        self._check(self._lib.nttmul_rns_forward_device(self._h, *args, batch, dev, stream or None))
+        self._check(self._c.forward_device(self._h, *args, batch, dev, stream or None))
 
     def inverse_device(self, out, a, batch: int, dev: Optional[int] = None, stream: int = 0):
         dev = self.first_dev if dev is None else dev
         args = self._dev_args((out, a), (batch,) * 2, dev)
-        self._check(self._lib.nttmul_rns_inverse_device(self._h, *args, batch, dev, stream or None))
+        self._check(self._c.inverse_device(self._h, *args, batch, dev, stream or None))
 
     def mac_ntt_device(self, c, a, b_hat, batch: int, terms: int, shared: bool = False,
                        dev: Optional[int] = None, stream: int = 0):
@@ -885,8 +933,8 @@ class RnsContext:
         dev = self.first_dev if dev is None else dev
         args = self._dev_args((c, a, b_hat),
                               (batch, batch * terms, terms if shared else batch * terms), dev)
-        self._check(self._lib.nttmul_rns_mac_ntt_device(self._h, *args, batch, terms, int(shared),
-                                                        dev, stream or None))
+        self._check(self._c.mac_ntt_device(self._h, *args, batch, terms, int(shared), dev,
+                                               stream or None))
 
     # host arrays
 
@@ -903,21 +951,21 @@ class RnsContext:
         if a.shape != b.shape:
             raise ValueError("a and b must have the same shape")
         c = np.empty_like(a)
-        self._check(self._lib.nttmul_rns_multiply(self._h, c.ctypes.data, a.ctypes.data,
-                                                  b.ctypes.data, a.shape[0]))
+        self._check(self._c.multiply(self._h, c.ctypes.data, a.ctypes.data, b.ctypes.data,
+                                         a.shape[0]))
         return c
 
     def forward(self, a) -> np.ndarray:
         a = self._host(a, 3, "a")
         out = np.empty_like(a)
-        self._check(self._lib.nttmul_rns_forward(self._h, out.ctypes.data, a.ctypes.data, a.shape[0]))
+        self._check(self._c.forward(self._h, out.ctypes.data, a.ctypes.data, a.shape[0]))
         return out
 
     def inverse(self, a_hat) -> np.ndarray:
         a_hat = self._host(a_hat, 3, "a_hat")
         out = np.empty_like(a_hat)
-        self._check(self._lib.nttmul_rns_inverse(self._h, out.ctypes.data, a_hat.ctypes.data,
-                                                 a_hat.shape[0]))
+        self._check(self._c.inverse(self._h, out.ctypes.data, a_hat.ctypes.data,
+                                        a_hat.shape[0]))
         return out
 
     def mac_ntt(self, a, b_hat, shared: bool = False) -> np.ndarray:
@@ -930,10 +978,31 @@ class RnsContext:
         if b_hat.shape != (a.shape[1:] if shared else a.shape):
             raise ValueError("b_hat must have a's shape, or [terms, limbs, n] when shared")
         c = np.empty((a.shape[0], self.limbs, self.n), dtype=self.io_dtype)
-        self._check(self._lib.nttmul_rns_mac_ntt(self._h, c.ctypes.data, a.ctypes.data,
-                                                 b_hat.ctypes.data, a.shape[0], a.shape[1],
-                                                 int(shared)))
+        self._check(self._c.mac_ntt(self._h, c.ctypes.data, a.ctypes.data, b_hat.ctypes.data,
+                                        a.shape[0], a.shape[1], int(shared)))
         return c
+
+
+class RnsContext(_RnsOps):
+    """nttmul_rns: the moduli q_0 .. q_{L-1} of one degree n <= 4096, every operation one launch
+    over [batch, limbs, n] operands (include/nttmul_rns.h).  Words are info.word_bits wide: 32
+    when every q_l < 2^31, 64 when every q_l >= 2^32.
+
+    Caller memory, as for Context: operands need the alignment of their word only; out may be the
+    input itself for forward and inverse, c must not overlap a, b or b_hat, and partial overlap is
+    never allowed; a call writes exactly batch * limbs * n words of its output and nothing else
+    in caller memory, and never writes an input."""
+    _PREFIX = "nttmul_rns"
+
+    def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False):
+        self._open_limbs(load_rns_library(), RnsInfo(), n, moduli, ndev, first_dev,
+                         _flags(validate, cyclic, share_devices))
+
+    def kernel_name(self, op) -> str:
+        """nttmul_rns_kernel_name for op 0..3 or "multiply" / "forward" / "inverse" / "mac", e.g.
+        "k_rns_rows<Arith32P3,u32,12>"."""
+        return self._kernel_name(op)
 
 
 # ---- RNS base conversion and ModDown (include/nttmul_bconv.h) ------------------------------------
@@ -941,8 +1010,6 @@ class RnsContext:
 BCONV_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_bconv.so")
 BCONV_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_bconv.h")
 BCONV_OPS = ("convert", "moddown")                    # nttmul_bconv_kernel_name's op numbers
-
-_BCONV_LIB: Optional[ctypes.CDLL] = None
 
 
 class BconvInfo(ctypes.Structure):
@@ -954,34 +1021,23 @@ class BconvInfo(ctypes.Structure):
 def load_bconv_library() -> ctypes.CDLL:
     """Load lib/libnttmul_bconv.so (include/nttmul_bconv.h): the ABI and kernels of
     libnttmul_rns.so plus the base-conversion kernels.  The other loaders are unaffected."""
-    global _BCONV_LIB
-    if _BCONV_LIB is not None:
-        return _BCONV_LIB
-    if not os.path.exists(BCONV_LIB_PATH):
-        raise ImportError(f"{BCONV_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
-    lib = _bind_rns(_bind_mac(_bind(ctypes.CDLL(BCONV_LIB_PATH))))
+    return _load_limb_library(BCONV_LIB_PATH, _bind_rns, _bind_bconv)
+
+
+def _bind_bconv(lib: ctypes.CDLL) -> None:
     vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
     u64p, prm = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_Params)
-    lib.nttmul_bconv_create.argtypes = [ctypes.POINTER(vp), prm, sz, u64p, u32, u64p, u32]
-    lib.nttmul_bconv_destroy.argtypes = [vp]
-    lib.nttmul_bconv_destroy.restype = None
-    lib.nttmul_bconv_last_error.argtypes = [vp]
-    lib.nttmul_bconv_last_error.restype = ctypes.c_char_p
-    lib.nttmul_bconv_get_info.argtypes = [vp, ctypes.POINTER(BconvInfo)]
+    _bind_handle(lib, "nttmul_bconv", BconvInfo, [u64p, u32, u64p, u32])
     lib.nttmul_bconv_plan.argtypes = [prm, sz, u64p, u32, u64p, u32, u64p, u64p, u64p]
     for op in BCONV_OPS:
         getattr(lib, f"nttmul_bconv_{op}_device").argtypes = [vp, vp, vp, sz, i32, vp]
         getattr(lib, f"nttmul_bconv_{op}").argtypes = [vp, vp, vp, sz]
     lib.nttmul_bconv_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
-    _BCONV_LIB = lib
-    return lib
 
 
 def bconv_exported_symbols() -> list:
     """Function names declared in include/nttmul_bconv.h."""
-    import re
-    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_bconv_\w+)\s*\(",
-                                 open(BCONV_HEADER_PATH).read(), re.M)))
+    return _header_symbols(BCONV_HEADER_PATH, "nttmul_bconv_")
 
 
 def _bconv_bases(n, from_q, to_q, flags):
@@ -1006,66 +1062,29 @@ def bconv_plan(n: int, from_q, to_q, flags: int = 0):
     return list(inv[:L]), [list(w[i * K:(i + 1) * K]) for i in range(L)], list(binv[:K])
 
 
-class BaseConverter:
+class BaseConverter(_Handle):
     """nttmul_bconv: conversion from the basis from_q (L primes) to the disjoint basis to_q
     (K primes) of one word class for one degree n <= 4096 (include/nttmul_bconv.h).  convert maps
     [batch, L, n] to [batch, K, n]; moddown maps [batch, K + L, n] (limbs of to_q, then of from_q)
     to [batch, K, n].  Words are word_bits wide."""
+    _PREFIX = "nttmul_bconv"
+    _OPS = BCONV_OPS
 
     def __init__(self, n: int, from_q, to_q, ndev: int = 1, first_dev: int = 0,
                  validate: bool = False, cyclic: bool = False, share_devices: bool = False):
-        self._lib = load_bconv_library()
-        self._h = ctypes.c_void_p()
-        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
-                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
-        from_q, to_q, prm, fq, tq = _bconv_bases(n, from_q, to_q, flags)
+        from_q, to_q, prm, fq, tq = _bconv_bases(n, from_q, to_q,
+                                                 _flags(validate, cyclic, share_devices))
         prm.ndev, prm.first_dev = ndev, first_dev
-        st = self._lib.nttmul_bconv_create(ctypes.byref(self._h), ctypes.byref(prm),
-                                           ctypes.sizeof(prm), fq, len(from_q), tq, len(to_q))
-        if st != NTTMUL_OK:
-            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
         info = BconvInfo()
-        self._lib.nttmul_bconv_get_info(self._h, ctypes.byref(info))
-        self.info = info
+        self._open(load_bconv_library(), info, prm, fq, len(from_q), tq, len(to_q))
         self.n, self.word_bits = info.n, info.word_bits
         self.from_limbs, self.to_limbs = info.from_limbs, info.to_limbs
         self.from_q, self.to_q = tuple(from_q), tuple(to_q)
         self.first_dev = first_dev
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.nttmul_bconv_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, st: int):
-        if st != NTTMUL_OK:
-            raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
-                                  f"{self._lib.nttmul_bconv_last_error(self._h).decode()}")
-
-    @property
-    def io_dtype(self):
-        return np.uint32 if self.word_bits == 32 else np.uint64
-
     def kernel_name(self, op) -> str:
         """nttmul_bconv_kernel_name for op 0..1 or "convert" / "moddown", e.g. "k_bconv<u32,0>"."""
-        op = BCONV_OPS.index(op) if isinstance(op, str) else int(op)
-        buf = ctypes.create_string_buffer(256)
-        st = self._lib.nttmul_bconv_kernel_name(self._h, op, buf, len(buf))
-        if st < 0:
-            self._check(st)
-        return buf.value.decode()
+        return self._kernel_name(op)
 
     def _in_limbs(self, op: str) -> int:
         return self.from_limbs + (self.to_limbs if op == "moddown" else 0)
@@ -1076,8 +1095,7 @@ class BaseConverter:
         dev = self.first_dev if dev is None else dev
         args = [_dev_arg(t, batch * k, self.n, self.word_bits, dev)
                 for t, k in ((out, self.to_limbs), (x, self._in_limbs(op)))]
-        fn = getattr(self._lib, f"nttmul_bconv_{op}_device")
-        self._check(fn(self._h, *args, batch, dev, stream or None))
+        self._check(getattr(self._c, f"{op}_device")(self._h, *args, batch, dev, stream or None))
 
     def convert_device(self, out, x, batch: int, dev: Optional[int] = None, stream: int = 0):
         """x [batch][from_limbs][n] -> out [batch][to_limbs][n]."""
@@ -1094,8 +1112,7 @@ class BaseConverter:
         if x.ndim != 3 or x.shape[1:] != (self._in_limbs(op), self.n):
             raise ValueError(f"{op}: x must have shape [batch, {self._in_limbs(op)}, {self.n}]")
         out = np.empty((x.shape[0], self.to_limbs, self.n), dtype=self.io_dtype)
-        fn = getattr(self._lib, f"nttmul_bconv_{op}")
-        self._check(fn(self._h, out.ctypes.data, x.ctypes.data, x.shape[0]))
+        self._check(getattr(self._c, op)(self._h, out.ctypes.data, x.ctypes.data, x.shape[0]))
         return out
 
     def convert(self, x) -> np.ndarray:
@@ -1115,8 +1132,6 @@ RNSMP_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_rnsmp.so")
 RNSMP_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_rnsmp.h")
 RNSMP_N = (8192, 16384, 32768, 65536)
 
-_RNSMP_LIB: Optional[ctypes.CDLL] = None
-
 
 class RnsMpInfo(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("limbs", ctypes.c_uint32),
@@ -1128,42 +1143,19 @@ def load_rnsmp_library() -> ctypes.CDLL:
     """Load lib/libnttmul_rnsmp.so (include/nttmul_rnsmp.h): the ABI and kernels of
     libnttmul_bconv.so plus the limb-aware multi-pass kernels.  The other loaders are
     unaffected."""
-    global _RNSMP_LIB
-    if _RNSMP_LIB is not None:
-        return _RNSMP_LIB
-    if not os.path.exists(RNSMP_LIB_PATH):
-        raise ImportError(f"{RNSMP_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
-    lib = _bind_rns(_bind_mac(_bind(ctypes.CDLL(RNSMP_LIB_PATH))))
-    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-    lib.nttmul_rnsmp_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(_Params), sz,
-                                        ctypes.POINTER(ctypes.c_uint64), u32]
-    lib.nttmul_rnsmp_destroy.argtypes = [vp]
-    lib.nttmul_rnsmp_destroy.restype = None
-    lib.nttmul_rnsmp_last_error.argtypes = [vp]
-    lib.nttmul_rnsmp_last_error.restype = ctypes.c_char_p
-    lib.nttmul_rnsmp_get_info.argtypes = [vp, ctypes.POINTER(RnsMpInfo)]
-    lib.nttmul_rnsmp_limb_info.argtypes = [vp, u32, ctypes.POINTER(Info)]
-    lib.nttmul_rnsmp_multiply_device.argtypes = [vp, vp, vp, vp, sz, i32, vp]
-    lib.nttmul_rnsmp_forward_device.argtypes = [vp, vp, vp, sz, i32, vp]
-    lib.nttmul_rnsmp_inverse_device.argtypes = [vp, vp, vp, sz, i32, vp]
-    lib.nttmul_rnsmp_mac_ntt_device.argtypes = [vp, vp, vp, vp, sz, u32, i32, i32, vp]
-    lib.nttmul_rnsmp_multiply.argtypes = [vp, vp, vp, vp, sz]
-    lib.nttmul_rnsmp_forward.argtypes = [vp, vp, vp, sz]
-    lib.nttmul_rnsmp_inverse.argtypes = [vp, vp, vp, sz]
-    lib.nttmul_rnsmp_mac_ntt.argtypes = [vp, vp, vp, vp, sz, u32, i32]
-    lib.nttmul_rnsmp_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
-    _RNSMP_LIB = lib
-    return lib
+    return _load_limb_library(RNSMP_LIB_PATH, _bind_rns, _bind_rnsmp)
+
+
+def _bind_rnsmp(lib: ctypes.CDLL) -> None:
+    _bind_rns(lib, "nttmul_rnsmp", RnsMpInfo)
 
 
 def rnsmp_exported_symbols() -> list:
     """Function names declared in include/nttmul_rnsmp.h."""
-    import re
-    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_rnsmp_\w+)\s*\(",
-                                 open(RNSMP_HEADER_PATH).read(), re.M)))
+    return _header_symbols(RNSMP_HEADER_PATH, "nttmul_rnsmp_")
 
 
-class RnsMpContext:
+class RnsMpContext(_RnsOps):
     """nttmul_rnsmp: the moduli q_0 .. q_{L-1} of one degree n in 8192 .. 65536, every pass of
     every operation one launch over [batch, limbs, n] operands (include/nttmul_rnsmp.h; n <= 4096
     is RnsContext's).  Words are info.word_bits wide: 32 when every q_l < 2^31, 64 when every
@@ -1178,148 +1170,18 @@ class RnsMpContext:
     Lifetime: one context serves any sequence of calls on any streams, from one host thread at a
     time (the scratch is handed between streams by an event).  close() does not wait for the
     streams passed to the *_device calls: synchronise them first."""
+    _PREFIX = "nttmul_rnsmp"
+    _NAME_CAP = 512
 
     def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
                  cyclic: bool = False, share_devices: bool = False, scratch_mb: int = 0):
-        self._lib = load_rnsmp_library()
-        self._h = ctypes.c_void_p()
-        moduli = [int(q) for q in moduli]
-        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
-                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
-        prm = _Params(n, 0, 0, ndev, first_dev, flags, 0, 0, 0, scratch_mb, 0)
-        qs = (ctypes.c_uint64 * max(1, len(moduli)))(*moduli)
-        st = self._lib.nttmul_rnsmp_create(ctypes.byref(self._h), ctypes.byref(prm),
-                                           ctypes.sizeof(prm), qs, len(moduli))
-        if st != NTTMUL_OK:
-            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
-        info = RnsMpInfo()
-        self._lib.nttmul_rnsmp_get_info(self._h, ctypes.byref(info))
-        self.info = info
-        self.n, self.limbs, self.word_bits = info.n, info.limbs, info.word_bits
-        self.moduli = tuple(moduli)
-        self.first_dev = first_dev
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.nttmul_rnsmp_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, st: int):
-        if st != NTTMUL_OK:
-            raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
-                                  f"{self._lib.nttmul_rnsmp_last_error(self._h).decode()}")
-
-    @property
-    def io_dtype(self):
-        return np.uint32 if self.word_bits == 32 else np.uint64
-
-    def limb_info(self, limb: int) -> Info:
-        """nttmul_rnsmp_limb_info: q, psi, omega, ... of one limb."""
-        info = Info()
-        self._check(self._lib.nttmul_rnsmp_limb_info(self._h, limb, ctypes.byref(info)))
-        return info
+        self._open_limbs(load_rnsmp_library(), RnsMpInfo(), n, moduli, ndev, first_dev,
+                         _flags(validate, cyclic, share_devices), scratch_mb)
 
     def kernel_name(self, op) -> str:
         """nttmul_rnsmp_kernel_name for op 0..3 or "multiply" / "forward" / "inverse" / "mac": the
         launch sequence, e.g. "k_rnsmp_cols_fwd<Arith64,u64,4,1> + k_rnsmp_xform<Arith64,u64,4,0>"."""
-        op = RNS_OPS.index(op) if isinstance(op, str) else int(op)
-        buf = ctypes.create_string_buffer(512)
-        st = self._lib.nttmul_rnsmp_kernel_name(self._h, op, buf, len(buf))
-        if st < 0:
-            self._check(st)
-        return buf.value.decode()
-
-    # device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`
-
-    def _dev_args(self, operands, polys, dev):
-        return [_dev_arg(t, k * self.limbs, self.n, self.word_bits, dev)
-                for t, k in zip(operands, polys)]
-
-    def multiply_device(self, c, a, b, batch: int, dev: Optional[int] = None, stream: int = 0):
-        """c, a, b: [batch][limbs][n]."""
-        dev = self.first_dev if dev is None else dev
-        args = self._dev_args((c, a, b), (batch,) * 3, dev)
-        self._check(self._lib.nttmul_rnsmp_multiply_device(self._h, *args, batch, dev, stream or None))
-
-    def forward_device(self, out, a, batch: int, dev: Optional[int] = None, stream: int = 0):
-        dev = self.first_dev if dev is None else dev
-        args = self._dev_args((out, a), (batch,) * 2, dev)
-        self._check(self._lib.nttmul_rnsmp_forward_device(self._h, *args, batch, dev, stream or None))
-
-    def inverse_device(self, out, a, batch: int, dev: Optional[int] = None, stream: int = 0):
-        dev = self.first_dev if dev is None else dev
-        args = self._dev_args((out, a), (batch,) * 2, dev)
-        self._check(self._lib.nttmul_rnsmp_inverse_device(self._h, *args, batch, dev, stream or None))
-
-    def mac_ntt_device(self, c, a, b_hat, batch: int, terms: int, shared: bool = False,
-                       dev: Optional[int] = None, stream: int = 0):
-        """a [batch][terms][limbs][n], b_hat likewise ([terms][limbs][n] when shared),
-        c [batch][limbs][n]."""
-        dev = self.first_dev if dev is None else dev
-        args = self._dev_args((c, a, b_hat),
-                              (batch, batch * terms, terms if shared else batch * terms), dev)
-        self._check(self._lib.nttmul_rnsmp_mac_ntt_device(self._h, *args, batch, terms,
-                                                          int(shared), dev, stream or None))
-
-    # host arrays
-
-    def _host(self, x, ndim, what):
-        x = np.ascontiguousarray(x, dtype=self.io_dtype)
-        if x.ndim != ndim or x.shape[-2:] != (self.limbs, self.n):
-            raise ValueError(f"{what} must have shape "
-                             f"[batch, {'terms, ' if ndim == 4 else ''}limbs, n]")
-        return x
-
-    def multiply(self, a, b) -> np.ndarray:
-        """c[p][l] = a[p][l] * b[p][l] mod (x^n + 1, q_l) for arrays of shape [batch, limbs, n]."""
-        a, b = self._host(a, 3, "a"), self._host(b, 3, "b")
-        if a.shape != b.shape:
-            raise ValueError("a and b must have the same shape")
-        c = np.empty_like(a)
-        self._check(self._lib.nttmul_rnsmp_multiply(self._h, c.ctypes.data, a.ctypes.data,
-                                                    b.ctypes.data, a.shape[0]))
-        return c
-
-    def forward(self, a) -> np.ndarray:
-        a = self._host(a, 3, "a")
-        out = np.empty_like(a)
-        self._check(self._lib.nttmul_rnsmp_forward(self._h, out.ctypes.data, a.ctypes.data,
-                                                   a.shape[0]))
-        return out
-
-    def inverse(self, a_hat) -> np.ndarray:
-        a_hat = self._host(a_hat, 3, "a_hat")
-        out = np.empty_like(a_hat)
-        self._check(self._lib.nttmul_rnsmp_inverse(self._h, out.ctypes.data, a_hat.ctypes.data,
-                                                   a_hat.shape[0]))
-        return out
-
-    def mac_ntt(self, a, b_hat, shared: bool = False) -> np.ndarray:
-        """a of shape [batch, terms, limbs, n]; b_hat of a's shape, or [terms, limbs, n] when
-        shared.  Returns c of shape [batch, limbs, n]."""
-        a = self._host(a, 4, "a")
-        b_hat = np.ascontiguousarray(b_hat, dtype=self.io_dtype)
-        if a.shape[1] == 0:
-            raise ValueError("terms must be > 0")
-        if b_hat.shape != (a.shape[1:] if shared else a.shape):
-            raise ValueError("b_hat must have a's shape, or [terms, limbs, n] when shared")
-        c = np.empty((a.shape[0], self.limbs, self.n), dtype=self.io_dtype)
-        self._check(self._lib.nttmul_rnsmp_mac_ntt(self._h, c.ctypes.data, a.ctypes.data,
-                                                   b_hat.ctypes.data, a.shape[0], a.shape[1],
-                                                   int(shared)))
-        return c
+        return self._kernel_name(op)
 
 
 # ---- Galois automorphisms over all RNS limbs (include/nttmul_galois.h) ---------------------------
@@ -1328,8 +1190,6 @@ GALOIS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_galois.so")
 GALOIS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_galois.h")
 GALOIS_OPS = ("coeff", "ntt", "ntt_many")             # nttmul_galois_kernel_name's op numbers
 GALOIS_MAX_COUNT = 16
-
-_GALOIS_LIB: Optional[ctypes.CDLL] = None
 
 
 class GaloisInfo(ctypes.Structure):
@@ -1340,21 +1200,13 @@ class GaloisInfo(ctypes.Structure):
 def load_galois_library() -> ctypes.CDLL:
     """Load lib/libnttmul_galois.so (include/nttmul_galois.h): the ABI and kernels of
     libnttmul_rnsmp.so plus the automorphism kernels.  The other loaders are unaffected."""
-    global _GALOIS_LIB
-    if _GALOIS_LIB is not None:
-        return _GALOIS_LIB
-    if not os.path.exists(GALOIS_LIB_PATH):
-        raise ImportError(f"{GALOIS_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
-    lib = _bind_rns(_bind_mac(_bind(ctypes.CDLL(GALOIS_LIB_PATH))))
+    return _load_limb_library(GALOIS_LIB_PATH, _bind_rns, _bind_galois)
+
+
+def _bind_galois(lib: ctypes.CDLL) -> None:
     vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
     u32p = ctypes.POINTER(u32)
-    lib.nttmul_galois_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(_Params), sz,
-                                         ctypes.POINTER(ctypes.c_uint64), u32]
-    lib.nttmul_galois_destroy.argtypes = [vp]
-    lib.nttmul_galois_destroy.restype = None
-    lib.nttmul_galois_last_error.argtypes = [vp]
-    lib.nttmul_galois_last_error.restype = ctypes.c_char_p
-    lib.nttmul_galois_get_info.argtypes = [vp, ctypes.POINTER(GaloisInfo)]
+    _bind_handle(lib, "nttmul_galois", GaloisInfo, [ctypes.POINTER(ctypes.c_uint64), u32])
     lib.nttmul_galois_limb_info.argtypes = [vp, u32, ctypes.POINTER(Info)]
     lib.nttmul_galois_element.argtypes = [u32, ctypes.c_int64, i32, u32p]
     lib.nttmul_galois_plan.argtypes = [u32, u32, vp, vp, vp]
@@ -1364,15 +1216,11 @@ def load_galois_library() -> ctypes.CDLL:
     lib.nttmul_galois_coeff.argtypes = [vp, vp, vp, u32, sz]
     lib.nttmul_galois_ntt.argtypes = [vp, vp, vp, u32, sz]
     lib.nttmul_galois_kernel_name.argtypes = [vp, i32, u32, ctypes.c_char_p, sz]
-    _GALOIS_LIB = lib
-    return lib
 
 
 def galois_exported_symbols() -> list:
     """Function names declared in include/nttmul_galois.h."""
-    import re
-    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_galois_\w+)\s*\(",
-                                 open(GALOIS_HEADER_PATH).read(), re.M)))
+    return _header_symbols(GALOIS_HEADER_PATH, "nttmul_galois_")
 
 
 def galois_element(n: int, step: int, conjugate: bool = False) -> int:
@@ -1402,7 +1250,7 @@ def galois_plan(n: int, k: int):
     return src, neg, hat
 
 
-class GaloisContext:
+class GaloisContext(_LimbContext):
     """nttmul_galois: the automorphisms sigma_k : a(x) -> a(x^k) mod (x^n + 1), k odd, over the
     moduli q_0 .. q_{L-1} of one degree n in 256 .. 65536, each call one launch over
     [batch, limbs, n] operands (include/nttmul_galois.h).  coeff_*: coefficient order, canonical
@@ -1416,73 +1264,21 @@ class GaloisContext:
 
     close() does not wait for the streams passed to the *_device calls: synchronise them first."""
 
+    _PREFIX = "nttmul_galois"
+    _OPS = GALOIS_OPS
+    _NAME_CAP = 128
+
     def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
                  cyclic: bool = False, share_devices: bool = False):
-        self._lib = load_galois_library()
-        self._h = ctypes.c_void_p()
-        moduli = [int(q) for q in moduli]
-        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
-                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
-        prm = _Params(n, 0, 0, ndev, first_dev, flags, 0, 0, 0, 0, 0)
-        qs = (ctypes.c_uint64 * max(1, len(moduli)))(*moduli)
-        st = self._lib.nttmul_galois_create(ctypes.byref(self._h), ctypes.byref(prm),
-                                            ctypes.sizeof(prm), qs, len(moduli))
-        if st != NTTMUL_OK:
-            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
-        info = GaloisInfo()
-        self._lib.nttmul_galois_get_info(self._h, ctypes.byref(info))
-        self.info = info
-        self.n, self.limbs, self.word_bits = info.n, info.limbs, info.word_bits
-        self.moduli = tuple(moduli)
-        self.first_dev = first_dev
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.nttmul_galois_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, st: int):
-        if st != NTTMUL_OK:
-            raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
-                                  f"{self._lib.nttmul_galois_last_error(self._h).decode()}")
-
-    @property
-    def io_dtype(self):
-        return np.uint32 if self.word_bits == 32 else np.uint64
-
-    def limb_info(self, limb: int) -> Info:
-        """nttmul_galois_limb_info: q, psi, omega, ... of one limb."""
-        info = Info()
-        self._check(self._lib.nttmul_galois_limb_info(self._h, limb, ctypes.byref(info)))
-        return info
+        self._open_limbs(load_galois_library(), GaloisInfo(), n, moduli, ndev, first_dev,
+                         _flags(validate, cyclic, share_devices))
 
     def kernel_name(self, op, count: int = 1) -> str:
         """nttmul_galois_kernel_name for op 0..2 or "coeff" / "ntt" / "ntt_many", e.g.
         "k_galois_coeff<u32,0>"."""
-        op = GALOIS_OPS.index(op) if isinstance(op, str) else int(op)
-        buf = ctypes.create_string_buffer(128)
-        st = self._lib.nttmul_galois_kernel_name(self._h, op, count, buf, len(buf))
-        if st < 0:
-            self._check(st)
-        return buf.value.decode()
+        return self._kernel_name(op, count)
 
     # device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`
-
-    def _dev_args(self, operands, polys, dev):
-        return [_dev_arg(t, k * self.limbs, self.n, self.word_bits, dev)
-                for t, k in zip(operands, polys)]
 
     def coeff_device(self, out, x, k: int, batch: int, dev: Optional[int] = None, stream: int = 0):
         """out = sigma_k(x) in coefficient order; out, x: [batch][limbs][n]."""
@@ -1539,8 +1335,6 @@ KS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_ks.so")
 KS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_ks.h")
 KS_OPS = ("modup", "moddown")                         # nttmul_ks_kernel_name's op numbers
 
-_KS_LIB: Optional[ctypes.CDLL] = None
-
 
 class KsInfo(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("q_limbs", ctypes.c_uint32),
@@ -1552,34 +1346,23 @@ class KsInfo(ctypes.Structure):
 def load_ks_library() -> ctypes.CDLL:
     """Load lib/libnttmul_ks.so (include/nttmul_ks.h): the ABI and kernels of libnttmul_galois.so
     plus the digit ModUp kernel.  The other loaders are unaffected."""
-    global _KS_LIB
-    if _KS_LIB is not None:
-        return _KS_LIB
-    if not os.path.exists(KS_LIB_PATH):
-        raise ImportError(f"{KS_LIB_PATH} not built: run __graft_entry__.build() or make -C {PKG_DIR}")
-    lib = _bind_rns(_bind_mac(_bind(ctypes.CDLL(KS_LIB_PATH))))
+    return _load_limb_library(KS_LIB_PATH, _bind_rns, _bind_ks)
+
+
+def _bind_ks(lib: ctypes.CDLL) -> None:
     vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
     u64p, prm = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_Params)
-    lib.nttmul_ks_create.argtypes = [ctypes.POINTER(vp), prm, sz, u64p, u32, u64p, u32, u32]
-    lib.nttmul_ks_destroy.argtypes = [vp]
-    lib.nttmul_ks_destroy.restype = None
-    lib.nttmul_ks_last_error.argtypes = [vp]
-    lib.nttmul_ks_last_error.restype = ctypes.c_char_p
-    lib.nttmul_ks_get_info.argtypes = [vp, ctypes.POINTER(KsInfo)]
+    _bind_handle(lib, "nttmul_ks", KsInfo, [u64p, u32, u64p, u32, u32])
     lib.nttmul_ks_plan.argtypes = [prm, sz, u64p, u32, u64p, u32, u32] + [vp] * 6
     for op in KS_OPS:
         getattr(lib, f"nttmul_ks_{op}_device").argtypes = [vp, vp, vp, sz, i32, vp]
         getattr(lib, f"nttmul_ks_{op}").argtypes = [vp, vp, vp, sz]
     lib.nttmul_ks_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
-    _KS_LIB = lib
-    return lib
 
 
 def ks_exported_symbols() -> list:
     """Function names declared in include/nttmul_ks.h."""
-    import re
-    return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(nttmul_ks_\w+)\s*\(",
-                                 open(KS_HEADER_PATH).read(), re.M)))
+    return _header_symbols(KS_HEADER_PATH, "nttmul_ks_")
 
 
 def _ks_bases(n, q, p, flags):
@@ -1614,7 +1397,7 @@ def ks_plan(n: int, q, p, digit_limbs: int, flags: int = 0):
     return inv, rows(w, M), rows(gadget, M), pinv, rows(pw, L), Pinv
 
 
-class KeySwitchBasis:
+class KeySwitchBasis(_Handle):
     """nttmul_ks: the bases Q = q (L primes) and P = p (K primes), disjoint and of one word class,
     with digits of digit_limbs limbs of Q, for one degree n in 256 .. 65536
     (include/nttmul_ks.h).  modup maps [batch, L, n] to [batch, digits, L + K, n], the operand `a`
@@ -1627,61 +1410,25 @@ class KeySwitchBasis:
 
     close() does not wait for the streams passed to the *_device calls: synchronise them first."""
 
+    _PREFIX = "nttmul_ks"
+    _OPS = KS_OPS
+    _NAME_CAP = 128
+
     def __init__(self, n: int, q, p, digit_limbs: int, ndev: int = 1, first_dev: int = 0,
                  validate: bool = False, cyclic: bool = False, share_devices: bool = False):
-        self._lib = load_ks_library()
-        self._h = ctypes.c_void_p()
-        flags = ((NTTMUL_FLAG_VALIDATE if validate else 0) | (NTTMUL_FLAG_CYCLIC if cyclic else 0)
-                 | (NTTMUL_FLAG_SHARE_DEVICES if share_devices else 0))
-        q, p, prm, qa, pa = _ks_bases(n, q, p, flags)
+        q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
         prm.ndev, prm.first_dev = ndev, first_dev
-        st = self._lib.nttmul_ks_create(ctypes.byref(self._h), ctypes.byref(prm),
-                                        ctypes.sizeof(prm), qa, len(q), pa, len(p), digit_limbs)
-        if st != NTTMUL_OK:
-            raise NttmulError(st, self._lib.nttmul_strerror(st).decode())
         info = KsInfo()
-        self._lib.nttmul_ks_get_info(self._h, ctypes.byref(info))
-        self.info = info
+        self._open(load_ks_library(), info, prm, qa, len(q), pa, len(p), digit_limbs)
         self.n, self.word_bits = info.n, info.word_bits
         self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
         self.digit_limbs, self.digits = info.digit_limbs, info.digits
         self.q, self.p = tuple(q), tuple(p)
         self.first_dev = first_dev
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.nttmul_ks_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, st: int):
-        if st != NTTMUL_OK:
-            raise NttmulError(st, f"{self._lib.nttmul_strerror(st).decode()}: "
-                                  f"{self._lib.nttmul_ks_last_error(self._h).decode()}")
-
-    @property
-    def io_dtype(self):
-        return np.uint32 if self.word_bits == 32 else np.uint64
-
     def kernel_name(self, op) -> str:
         """nttmul_ks_kernel_name for op 0..1 or "modup" / "moddown", e.g. "k_ks_modup<u32>"."""
-        op = KS_OPS.index(op) if isinstance(op, str) else int(op)
-        buf = ctypes.create_string_buffer(128)
-        st = self._lib.nttmul_ks_kernel_name(self._h, op, buf, len(buf))
-        if st < 0:
-            self._check(st)
-        return buf.value.decode()
+        return self._kernel_name(op)
 
     def _limbs(self, op: str):
         """(output, input) limb polynomials per batch entry."""

@@ -1,5 +1,6 @@
 // ks_san.cpp — the host-only entry point of include/nttmul_ks.h (csrc/ks_plan.cpp: nttmul_ks_plan,
-// over csrc/planner.cpp's modular arithmetic) under ASan / UBSan, with a main of its own
+// over csrc/basis.cpp's create-time checks and csrc/planner.cpp's modular arithmetic) under ASan /
+// UBSan, with a main of its own
 // (tests/test_ks_sanitizers.py).  Every table is a heap block of exactly its stated size, so a
 // write past either end is a report; the results are checked against the definitions, computed
 // here another way (running products in 128-bit integers, inverses checked by multiplying back).

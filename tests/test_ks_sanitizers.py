@@ -1,6 +1,7 @@
 """An ASan/UBSan CPU build of the host-only entry point of include/nttmul_ks.h (nttmul_ks_plan:
-csrc/ks_plan.cpp as it stands, with the planner's modular arithmetic of csrc/planner.cpp, the part
-of the host code that needs no device), driven by the stand-alone program
+csrc/ks_plan.cpp as it stands, with the create-time checks of csrc/basis.cpp that every limb-aware
+library shares and the planner's modular arithmetic of csrc/planner.cpp, the part of the host code
+that needs no device), driven by the stand-alone program
 tests/sanitize/ks_san.cpp, which also checks the results.  Any sanitizer report fails the run
 (-fno-sanitize-recover=all).  Nothing is loaded into Python."""
 import os
@@ -21,7 +22,8 @@ def test_asan_ubsan_ks_host_code(tmp_path):
     subprocess.run(["g++", "-std=c++17", *san, "-I", os.path.join(ROOT, "include"), "-I", CSRC,
                     "-o", str(exe),
                     os.path.join(ROOT, "tests", "sanitize", "ks_san.cpp"),
-                    os.path.join(CSRC, "ks_plan.cpp"), os.path.join(CSRC, "planner.cpp")],
+                    os.path.join(CSRC, "ks_plan.cpp"), os.path.join(CSRC, "basis.cpp"),
+                    os.path.join(CSRC, "planner.cpp")],
                    check=True)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
