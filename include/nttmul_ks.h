@@ -67,7 +67,8 @@
  *
  * Out of scope here:
  *   - one call that runs the whole key switch on scratch of its own;
- *   - a mac that shares the forward transforms between the two key components;
+ *   - a mac that shares the forward transforms between the two key components: that is
+ *     nttmul_macn.h (lib/libnttmul_macn.so), whose one call replaces the two mac_ntt calls above;
  *   - NTT-domain input or output, that is a fused inverse -> modup -> forward pipeline;
  *   - exact conversion (the alpha correction), and rounding instead of flooring in moddown;
  *   - raising nttmul_bconv_create's own n limit (it stays at 4096);

@@ -108,11 +108,11 @@ int op_args(bool have_ctx, int op, const void *c, const void *a, const void *b, 
 }
 
 void op_words(uint32_t limbs, uint32_t n, int op, size_t batch, uint32_t terms, int shared,
-              size_t words[3]) {
+              size_t words[3], uint32_t comps) {
   const size_t poly = (size_t)limbs * n;
-  words[0] = batch * poly;
+  words[0] = batch * comps * poly;
   words[1] = op == kRnsMac ? batch * terms * poly : batch * poly;
-  words[2] = op == kRnsMac ? (shared ? 1 : batch) * terms * poly
+  words[2] = op == kRnsMac ? (shared ? 1 : batch) * comps * terms * poly
                            : op == kRnsMultiply ? batch * poly : 0;
 }
 
@@ -124,47 +124,65 @@ RnsTables view(const nttmul_rns *r, const RnsDev &d) {
   return tables_for(r->logn, r->limbs, r->word_bits, d.tw, d.tab, d.base.q);
 }
 
-// on d (the current device), stream s
+// on d (the current device), stream s.  launch: a sibling's kernel in launch_rns's place, with
+// comps operands per term (rns.hpp rns_mac_comps)
 int run(nttmul_rns *r, RnsDev &d, int op, void *c, const void *a, const void *b, size_t batch,
-        uint32_t terms, int shared, hipStream_t s) {
+        uint32_t terms, int shared, hipStream_t s, uint32_t comps = 1,
+        RnsMacLaunch launch = nullptr) {
   if (!batch) return NTTMUL_OK;
   if (r->flags & NTTMUL_FLAG_VALIDATE) {
     size_t words[3];
-    op_words(r->limbs, r->n, op, batch, terms, shared, words);
+    op_words(r->limbs, r->n, op, batch, terms, shared, words, comps);
     if (const int st = check_range(r->err, d.base.flag, d.base.q, r->limbs, r->logn, r->word_bits,
                                    a, words[1], b, words[2],
                                    "input coefficient >= its limb's modulus", s))
       return st;
   }
-  LIMB_TRY(r->err, launch_rns(view(r, d), op, c, a, b, batch, terms, shared, s));
+  if (launch)
+    LIMB_TRY(r->err, launch(view(r, d), c, a, b, batch, terms, comps, shared, s));
+  else
+    LIMB_TRY(r->err, launch_rns(view(r, d), op, c, a, b, batch, terms, shared, s));
   return NTTMUL_OK;
 }
 
 int device_op(nttmul_rns *r, int op, void *c, const void *a, const void *b, size_t batch,
-              uint32_t terms, int shared, int dev, void *stream) {
+              uint32_t terms, int shared, int dev, void *stream, uint32_t comps = 1,
+              RnsMacLaunch launch = nullptr) {
   if (const int st = op_args(r != nullptr, op, c, a, b, batch, terms)) return st;
   return on_device(r->err, r->dev, r->ndev, dev, [&](RnsDev &d) {
-    return run(r, d, op, c, a, b, batch, terms, shared, (hipStream_t)stream);
+    return run(r, d, op, c, a, b, batch, terms, shared, (hipStream_t)stream, comps, launch);
   });
 }
 
 // Host buffers: dev[0], device buffers owned by the call, the device path, copy back, synchronise
 int host_op(nttmul_rns *r, int op, void *c, const void *a, const void *b, size_t batch,
-            uint32_t terms, int shared) {
+            uint32_t terms, int shared, uint32_t comps = 1, RnsMacLaunch launch = nullptr) {
   if (const int st = op_args(r != nullptr, op, c, a, b, batch, terms)) return st;
   if (!batch) return NTTMUL_OK;
   RnsDev &d = r->dev[0];
   size_t words[3];
-  op_words(r->limbs, r->n, op, batch, terms, shared, words);
+  op_words(r->limbs, r->n, op, batch, terms, shared, words, comps);
   const size_t wb = (size_t)r->word_bits / 8;
   const Staged ops[3] = {{nullptr, c, words[0] * wb}, {a, nullptr, words[1] * wb},
                          {b, nullptr, words[2] * wb}};
   return staged_op(r->err, d.base, "rns", ops, 3, [&](void *const *buf) {
-    return run(r, d, op, buf[0], buf[1], buf[2], batch, terms, shared, d.base.stream);
+    return run(r, d, op, buf[0], buf[1], buf[2], batch, terms, shared, d.base.stream, comps,
+               launch);
   });
 }
 
 }  // namespace
+
+namespace nttmul {
+
+int rns_mac_comps(nttmul_rns *r, RnsMacLaunch launch, void *c, const void *a, const void *b_hat,
+                  size_t batch, uint32_t terms, uint32_t comps, int shared, int host, int dev,
+                  void *stream) {
+  if (host) return host_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, comps, launch);
+  return device_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, dev, stream, comps, launch);
+}
+
+}  // namespace nttmul
 
 extern "C" {
 

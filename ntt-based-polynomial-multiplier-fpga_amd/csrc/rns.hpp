@@ -6,6 +6,8 @@
 
 #include "launch.hpp"
 
+struct nttmul_rns;  // include/nttmul_rns.h; defined in rns.cpp
+
 namespace nttmul {
 
 // The kernel families of an RNS context.  Each reads its own per-device table of KParams<A>, one
@@ -60,14 +62,30 @@ RnsTables tables_for(uint32_t logn, uint32_t limbs, int word_bits, const void *t
 // What a call decides before any device access (have_ctx: the handle is not NULL)
 int op_args(bool have_ctx, int op, const void *c, const void *a, const void *b, size_t batch,
             uint32_t terms);
-// words of the operands of one call: c, a, b (b 0 for the transforms)
+// words of the operands of one call: c, a, b (b 0 for the transforms).  comps: the mac's b_hat
+// components per term, each with an output polynomial of its own (1 but for macn.cpp)
 void op_words(uint32_t limbs, uint32_t n, int op, size_t batch, uint32_t terms, int shared,
-              size_t words[3]);
+              size_t words[3], uint32_t comps = 1);
 // One device's stream, moduli, flag and tables at create: the limbs' twiddles in one allocation
 // *tw (fw, iw of limb 0, fw, iw of limb 1, ...), then the three KParams tables tab[] that `fill`
 // (rns_fill_entry or rnsmp_fill_entry) builds from pointers into it
 int upload_limb_tables(char *err, const std::vector<Plan> &plan, int word_bits, LimbDev &d,
                        void **tw, void *tab[kRnsFamilies],
                        hipError_t (*fill)(const LaunchTables &, int, void *));
+
+
+// ---- for a sibling library that adds a mac kernel on the same context (macn.cpp) ----------------
+
+// launch_rns's place in a call: c [batch][comps][limbs][n], b = b_hat
+// [batch or 1][comps][terms][limbs][n]
+using RnsMacLaunch = hipError_t (*)(const RnsTables &T, void *c, const void *a, const void *b,
+                                    size_t batch, uint32_t terms, uint32_t comps, int shared,
+                                    hipStream_t s);
+// nttmul_rns_mac_ntt (host != 0; dev and stream unused) or nttmul_rns_mac_ntt_device with `comps`
+// operands per term and `launch` for the launch: the same argument checks, device selection,
+// range check (over all of b_hat) and error text
+int rns_mac_comps(nttmul_rns *r, RnsMacLaunch launch, void *c, const void *a, const void *b_hat,
+                  size_t batch, uint32_t terms, uint32_t comps, int shared, int host, int dev,
+                  void *stream);
 
 }  // namespace nttmul

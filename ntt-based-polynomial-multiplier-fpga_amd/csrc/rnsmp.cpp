@@ -20,6 +20,7 @@
 #include "nttmul_rnsmp.h"
 #include "planner.hpp"
 #include "rnsmp.hpp"
+#include "subbatch.hpp"
 
 using namespace nttmul;
 
@@ -86,39 +87,44 @@ int ensure(nttmul_rnsmp *r, MpScratch &sc, int i, size_t need) {
 }
 
 // on d (the current device), stream s: the range check, then sub-batches of whole polynomials
-// through the scratch
+// through the scratch.  launch: a sibling's launches in launch_rnsmp's place, with comps operands
+// per term and as many output polynomials per batch entry (rnsmp.hpp rnsmp_mac_comps)
 int run(nttmul_rnsmp *r, MpDev &d, int op, void *c, const void *a, const void *b, size_t batch,
-        uint32_t terms, int shared, hipStream_t s) {
+        uint32_t terms, int shared, hipStream_t s, uint32_t comps = 1,
+        MpMacLaunch launch = nullptr) {
   if (!batch) return NTTMUL_OK;
   const RnsTables T = view(r, d);
   if (r->flags & NTTMUL_FLAG_VALIDATE) {
     size_t words[3];
-    op_words(r->limbs, r->n, op, batch, terms, shared, words);
+    op_words(r->limbs, r->n, op, batch, terms, shared, words, comps);
     if (const int st = check_range(r->err, d.base.flag, d.base.q, r->limbs, r->logn, r->word_bits,
                                    a, words[1], b, words[2],
                                    "input coefficient >= its limb's modulus", s))
       return st;
   }
-  // bytes of one polynomial (all limbs) in a scratch buffer, and of one polynomial's a: for the
-  // mac all its terms, so that no scratch buffer of a sub-batch exceeds scratch_mb
+  // bytes of one polynomial (all limbs) in a scratch buffer, of one polynomial's a (for the mac
+  // all its terms) and of its output (all components), so that no scratch buffer of a sub-batch
+  // exceeds scratch_mb
   const size_t poly = (size_t)r->limbs * r->n * (r->word_bits / 8);
-  const size_t apoly = op == kRnsMac ? poly * terms : poly;
-  const size_t chunk =
-      std::max<size_t>(1, std::min(batch, ((size_t)r->scratch_mb << 20) / apoly));
+  const size_t apoly = op == kRnsMac ? poly * terms : poly, cpoly = poly * comps;
+  const size_t chunk = mp_chunk((size_t)r->scratch_mb << 20, apoly, cpoly, batch);
   MpScratch &sc = d.scr;
   if (!sc.ev) LIMB_TRY(r->err, hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming));
   if (sc.used && sc.last != s) LIMB_TRY(r->err, hipStreamWaitEvent(s, sc.ev, 0));
   const bool two = op == kRnsMultiply, three = op == kRnsMultiply || op == kRnsMac;
   int st = ensure(r, sc, 0, chunk * apoly);
   if (!st && two) st = ensure(r, sc, 1, chunk * poly);
-  if (!st && three) st = ensure(r, sc, 2, chunk * poly);
+  if (!st && three) st = ensure(r, sc, 2, chunk * cpoly);
   if (st) return st;
-  const size_t bstep = op == kRnsMac ? (shared ? 0 : apoly) : poly;
-  for (size_t p = 0; p < batch && !st; p += chunk) {
-    const size_t cnt = std::min(chunk, batch - p);
+  const size_t bstep = op == kRnsMac ? (shared ? 0 : apoly * comps) : poly;
+  for (size_t k = 0; k < mp_subs(batch, chunk) && !st; k++) {
+    const MpSub u = mp_sub(batch, chunk, k);
+    void *cu = (char *)c + u.p * cpoly;
+    const void *au = (const char *)a + u.p * apoly;
+    const void *bu = b ? (const char *)b + u.p * bstep : nullptr;
     const hipError_t e =
-        launch_rnsmp(T, op, (char *)c + p * poly, (const char *)a + p * apoly,
-                     b ? (const char *)b + p * bstep : nullptr, cnt, terms, shared, sc.buf, s);
+        launch ? launch(T, cu, au, bu, u.cnt, terms, comps, shared, sc.buf, s)
+               : launch_rnsmp(T, op, cu, au, bu, u.cnt, terms, shared, sc.buf, s);
     if (e != hipSuccess) st = fail(r->err, e, "sub-batch launch");
   }
   // (also after a failure: what was enqueued still uses the scratch)
@@ -130,30 +136,43 @@ int run(nttmul_rnsmp *r, MpDev &d, int op, void *c, const void *a, const void *b
 }
 
 int device_op(nttmul_rnsmp *r, int op, void *c, const void *a, const void *b, size_t batch,
-              uint32_t terms, int shared, int dev, void *stream) {
+              uint32_t terms, int shared, int dev, void *stream, uint32_t comps = 1,
+              MpMacLaunch launch = nullptr) {
   if (const int st = op_args(r != nullptr, op, c, a, b, batch, terms)) return st;
   return on_device(r->err, r->dev, r->ndev, dev, [&](MpDev &d) {
-    return run(r, d, op, c, a, b, batch, terms, shared, (hipStream_t)stream);
+    return run(r, d, op, c, a, b, batch, terms, shared, (hipStream_t)stream, comps, launch);
   });
 }
 
 // Host buffers: dev[0], device buffers owned by the call, the device path, copy back, synchronise
 int host_op(nttmul_rnsmp *r, int op, void *c, const void *a, const void *b, size_t batch,
-            uint32_t terms, int shared) {
+            uint32_t terms, int shared, uint32_t comps = 1, MpMacLaunch launch = nullptr) {
   if (const int st = op_args(r != nullptr, op, c, a, b, batch, terms)) return st;
   if (!batch) return NTTMUL_OK;
   MpDev &d = r->dev[0];
   size_t words[3];
-  op_words(r->limbs, r->n, op, batch, terms, shared, words);
+  op_words(r->limbs, r->n, op, batch, terms, shared, words, comps);
   const size_t wb = (size_t)r->word_bits / 8;
   const Staged ops[3] = {{nullptr, c, words[0] * wb}, {a, nullptr, words[1] * wb},
                          {b, nullptr, words[2] * wb}};
   return staged_op(r->err, d.base, "rnsmp", ops, 3, [&](void *const *buf) {
-    return run(r, d, op, buf[0], buf[1], buf[2], batch, terms, shared, d.base.stream);
+    return run(r, d, op, buf[0], buf[1], buf[2], batch, terms, shared, d.base.stream, comps,
+               launch);
   });
 }
 
 }  // namespace
+
+namespace nttmul {
+
+int rnsmp_mac_comps(nttmul_rnsmp *r, MpMacLaunch launch, void *c, const void *a, const void *b_hat,
+                    size_t batch, uint32_t terms, uint32_t comps, int shared, int host, int dev,
+                    void *stream) {
+  if (host) return host_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, comps, launch);
+  return device_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, dev, stream, comps, launch);
+}
+
+}  // namespace nttmul
 
 extern "C" {
 

@@ -140,6 +140,30 @@ static hipError_t dispatch_words(const RnsTables &T, int op, void *c, const void
              : dispatch<Arith64, uint64_t>(T, op, c, a, b, batch, terms, shared, scr, E);
 }
 
+template <class A, class IO>
+static hipError_t cols_only(const RnsTables &T, int dir, void *out, const void *in, size_t units,
+                            const Emit &E) {
+  const auto go = [&](auto l1) {
+    constexpr int L1 = decltype(l1)::value;
+    return dir ? cols_inv<A, IO, L1>(T, kRnsTransform, in, out, units, E)
+               : cols_fwd<A, IO, L1, 1>(T, kRnsTransform, in, nullptr, out, nullptr, units, E);
+  };
+  switch (T.logn) {
+    case 13: return go(std::integral_constant<int, 1>{});
+    case 14: return go(std::integral_constant<int, 2>{});
+    case 15: return go(std::integral_constant<int, 3>{});
+    case 16: return go(std::integral_constant<int, 4>{});
+    default: return hipErrorNotSupported;
+  }
+}
+
+hipError_t launch_rnsmp_cols(const RnsTables &T, int dir, void *out, const void *in, size_t units,
+                             hipStream_t s, std::string *describe) {
+  const Emit E{s, describe};
+  return T.word_bits == 32 ? cols_only<Arith32P, uint32_t>(T, dir, out, in, units, E)
+                           : cols_only<Arith64, uint64_t>(T, dir, out, in, units, E);
+}
+
 hipError_t launch_rnsmp(const RnsTables &T, int op, void *c, const void *a, const void *b,
                         size_t batch, uint32_t terms, int shared, void *const *scr, hipStream_t s) {
   return dispatch_words(T, op, c, a, b, batch, terms, shared, scr, Emit{s, nullptr});

@@ -5,6 +5,8 @@
 #pragma once
 #include "rns.hpp"
 
+struct nttmul_rnsmp;  // include/nttmul_rnsmp.h; defined in rnsmp.cpp
+
 namespace nttmul {
 
 // The entry of family `fam` for one limb of a multi-pass context (logn 13 .. 16), written to host
@@ -25,5 +27,29 @@ hipError_t launch_rnsmp(const RnsTables &T, int op, void *c, const void *a, cons
 // The kernels launch_rnsmp launches for (T, op), joined by " + ": the dry run of the launching
 // statements themselves (kernels_dev.hpp Emit)
 hipError_t describe_rnsmp(const RnsTables &T, int op, std::string *out);
+
+// ---- for a sibling library that adds a row pass on the same context (macn.hip, macn.cpp) --------
+
+// The mac's column passes alone, as launch_rnsmp launches them (tab kRnsTransform): dir 0
+// k_rnsmp_cols_fwd<.., 1> over `units` polynomials of caller memory `in` to the scratch `out`,
+// dir 1 k_rnsmp_cols_inv over `units` polynomials of the scratch `in` to caller memory `out`.
+// With `describe` set nothing is launched and the kernel's name is appended to it, " + " between
+// names.
+hipError_t launch_rnsmp_cols(const RnsTables &T, int dir, void *out, const void *in, size_t units,
+                             hipStream_t s, std::string *describe);
+
+// launch_rnsmp's place in a sub-batch: c [batch][comps][limbs][n], b = b_hat
+// [batch or 1][comps][terms][limbs][n]; scr[0] holds batch terms polynomials, scr[2] batch comps
+using MpMacLaunch = hipError_t (*)(const RnsTables &T, void *c, const void *a, const void *b,
+                                   size_t batch, uint32_t terms, uint32_t comps, int shared,
+                                   void *const *scr, hipStream_t s);
+// nttmul_rnsmp_mac_ntt (host != 0; dev and stream unused) or nttmul_rnsmp_mac_ntt_device with
+// `comps` operands per term and `launch` for a sub-batch's launches: the same argument checks,
+// device selection, range check (over all of b_hat), scratch hand-over and error text.  The
+// sub-batch (subbatch.hpp mp_chunk) also keeps comps output polynomials per batch entry within
+// scratch_mb.
+int rnsmp_mac_comps(nttmul_rnsmp *r, MpMacLaunch launch, void *c, const void *a, const void *b_hat,
+                    size_t batch, uint32_t terms, uint32_t comps, int shared, int host, int dev,
+                    void *stream);
 
 }  // namespace nttmul

@@ -1476,6 +1476,101 @@ class KeySwitchBasis(_Handle):
         return self._host("moddown", x)
 
 
+# ---- the mac against several NTT-domain operands (include/nttmul_macn.h) -------------------------
+
+MACN_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_macn.so")
+MACN_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_macn.h")
+MACN_MAX_COMPS = 2
+
+
+def load_macn_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_macn.so (include/nttmul_macn.h): the ABI and kernels of libnttmul_ks.so
+    plus the mac against several NTT-domain operands.  The other loaders are unaffected."""
+    return _load_limb_library(MACN_LIB_PATH, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn)
+
+
+def _bind_macn(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    for prefix in ("nttmul_rns", "nttmul_rnsmp"):
+        getattr(lib, f"{prefix}_macn_ntt_device").argtypes = [vp, vp, vp, vp, sz, u32, u32, i32,
+                                                              i32, vp]
+        getattr(lib, f"{prefix}_macn_ntt").argtypes = [vp, vp, vp, vp, sz, u32, u32, i32]
+        getattr(lib, f"{prefix}_macn_kernel_name").argtypes = [vp, u32, ctypes.c_char_p, sz]
+
+
+def macn_exported_symbols() -> list:
+    """Function names declared in include/nttmul_macn.h."""
+    return _header_symbols(MACN_HEADER_PATH, "nttmul_rns")
+
+
+class _MacnOps:
+    """What RnsMacnContext and RnsMpMacnContext add to their context:
+    c[p][i] = INTT(sum_t NTT(a[p][t]) o b_hat[p or shared][i][t]) for i < comps, the forward
+    transforms of a shared by the components.  Component i equals mac_ntt against b_hat[..][i] bit
+    for bit.
+
+    Caller memory: operands need the alignment of their word only; c must overlap neither a nor
+    b_hat; a call writes exactly batch * comps * limbs * n words of c and never writes an input."""
+
+    def macn_kernel_name(self, comps: int) -> str:
+        """<prefix>_macn_kernel_name, e.g. "k_rns_macn<Arith32P,u32,12,2>"; comps = 1 names the
+        context's mac."""
+        buf = ctypes.create_string_buffer(self._NAME_CAP)
+        st = self._c.macn_kernel_name(self._h, comps, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def macn_ntt_device(self, c, a, b_hat, batch: int, terms: int, comps: int,
+                        shared: bool = True, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        a [batch][terms][limbs][n], b_hat [comps][terms][limbs][n] when shared, or
+        [batch][comps][terms][limbs][n]; c [batch][comps][limbs][n]."""
+        dev = self.first_dev if dev is None else dev
+        args = self._dev_args((c, a, b_hat), (batch * comps, batch * terms,
+                                              (1 if shared else batch) * comps * terms), dev)
+        self._check(self._c.macn_ntt_device(self._h, *args, batch, terms, comps, int(shared), dev,
+                                            stream or None))
+
+    def macn_ntt(self, a, b_hat, shared: bool = True) -> np.ndarray:
+        """a of shape [batch, terms, limbs, n]; b_hat of shape [comps, terms, limbs, n] when
+        shared, or [batch, comps, terms, limbs, n].  Returns c of shape [batch, comps, limbs, n]."""
+        a = self._host(a, 4, "a")
+        b_hat = np.ascontiguousarray(b_hat, dtype=self.io_dtype)
+        if a.shape[1] == 0:
+            raise ValueError("terms must be > 0")
+        if b_hat.ndim != (4 if shared else 5) or b_hat.shape[-3:] != a.shape[1:] \
+                or (not shared and b_hat.shape[0] != a.shape[0]):
+            raise ValueError("b_hat must have shape [comps, terms, limbs, n] when shared, or "
+                             "[batch, comps, terms, limbs, n]")
+        comps = b_hat.shape[-4]
+        c = np.empty((a.shape[0], comps, self.limbs, self.n), dtype=self.io_dtype)
+        self._check(self._c.macn_ntt(self._h, c.ctypes.data, a.ctypes.data, b_hat.ctypes.data,
+                                     a.shape[0], a.shape[1], comps, int(shared)))
+        return c
+
+
+class RnsMacnContext(_MacnOps, RnsContext):
+    """An RnsContext created through lib/libnttmul_macn.so: every RnsContext method, plus
+    macn_ntt (include/nttmul_macn.h), for n <= 4096."""
+
+    def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False):
+        self._open_limbs(load_macn_library(), RnsInfo(), n, moduli, ndev, first_dev,
+                         _flags(validate, cyclic, share_devices))
+
+
+class RnsMpMacnContext(_MacnOps, RnsMpContext):
+    """An RnsMpContext created through lib/libnttmul_macn.so: every RnsMpContext method, plus
+    macn_ntt (include/nttmul_macn.h), for n in 8192 .. 65536.  A sub-batch keeps both
+    batch * terms and batch * comps polynomials within scratch_mb."""
+
+    def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False, scratch_mb: int = 0):
+        self._open_limbs(load_macn_library(), RnsMpInfo(), n, moduli, ndev, first_dev,
+                         _flags(validate, cyclic, share_devices), scratch_mb)
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
