@@ -56,7 +56,8 @@
  * not wait for the streams passed to the *_device calls: synchronise them first.
  *
  * Out of scope here:
- *   - automorphisms fused into the mac or the transforms;
+ *   - automorphisms fused into the transforms (fused into the mac against NTT-domain operands:
+ *     include/nttmul_hoist.h, lib/libnttmul_hoist.so);
  *   - a coefficient-order `many`;
  *   - in-place forms;
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC), the class 2^31 <= q < 2^32;

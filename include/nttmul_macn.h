@@ -61,8 +61,8 @@
  *
  * Out of scope here:
  *   - more than two components;
- *   - NTT-domain a (the hoisted rotation: nttmul_galois_ntt_many on transformed digits, then a
- *     pointwise mac);
+ *   - NTT-domain a (the hoisted rotation is include/nttmul_hoist.h, lib/libnttmul_hoist.so: a
+ *     pointwise mac on transformed digits with the automorphism fused into their load);
  *   - a fused modup -> mac or mac -> moddown;
  *   - one call that runs the whole key switch on scratch of its own;
  *   - a bench.py mode (tools/bench_macn.py measures these calls).

@@ -53,7 +53,8 @@ static hipError_t rns_macn_words(const RnsTables &T, void *c, const void *a, con
 }
 
 hipError_t launch_rns_macn(const RnsTables &T, void *c, const void *a, const void *b, size_t batch,
-                           uint32_t terms, uint32_t comps, int shared, hipStream_t s) {
+                           uint32_t terms, uint32_t comps, int shared, hipStream_t s,
+                           const void *) {
   return rns_macn_words(T, c, a, b, batch, terms, comps, shared, Emit{s, nullptr});
 }
 

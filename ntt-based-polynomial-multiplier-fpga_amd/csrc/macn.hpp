@@ -10,7 +10,8 @@ namespace nttmul {
 // a [batch][terms][limbs][n], b = b_hat [batch or 1][comps][terms][limbs][n],
 // c [batch][comps][limbs][n]; n <= 4096, comps >= 2
 hipError_t launch_rns_macn(const RnsTables &T, void *c, const void *a, const void *b, size_t batch,
-                           uint32_t terms, uint32_t comps, int shared, hipStream_t s);
+                           uint32_t terms, uint32_t comps, int shared, hipStream_t s,
+                           const void *aux);
 // "k_rns_macn<Arith32P,u32,12,2>": the dry run of the launching statement itself
 hipError_t describe_rns_macn(const RnsTables &T, uint32_t comps, std::string *out);
 

@@ -128,7 +128,7 @@ RnsTables view(const nttmul_rns *r, const RnsDev &d) {
 // comps operands per term (rns.hpp rns_mac_comps)
 int run(nttmul_rns *r, RnsDev &d, int op, void *c, const void *a, const void *b, size_t batch,
         uint32_t terms, int shared, hipStream_t s, uint32_t comps = 1,
-        RnsMacLaunch launch = nullptr) {
+        RnsMacLaunch launch = nullptr, const void *aux = nullptr) {
   if (!batch) return NTTMUL_OK;
   if (r->flags & NTTMUL_FLAG_VALIDATE) {
     size_t words[3];
@@ -139,7 +139,7 @@ int run(nttmul_rns *r, RnsDev &d, int op, void *c, const void *a, const void *b,
       return st;
   }
   if (launch)
-    LIMB_TRY(r->err, launch(view(r, d), c, a, b, batch, terms, comps, shared, s));
+    LIMB_TRY(r->err, launch(view(r, d), c, a, b, batch, terms, comps, shared, s, aux));
   else
     LIMB_TRY(r->err, launch_rns(view(r, d), op, c, a, b, batch, terms, shared, s));
   return NTTMUL_OK;
@@ -147,16 +147,18 @@ int run(nttmul_rns *r, RnsDev &d, int op, void *c, const void *a, const void *b,
 
 int device_op(nttmul_rns *r, int op, void *c, const void *a, const void *b, size_t batch,
               uint32_t terms, int shared, int dev, void *stream, uint32_t comps = 1,
-              RnsMacLaunch launch = nullptr) {
+              RnsMacLaunch launch = nullptr, const void *aux = nullptr) {
   if (const int st = op_args(r != nullptr, op, c, a, b, batch, terms)) return st;
   return on_device(r->err, r->dev, r->ndev, dev, [&](RnsDev &d) {
-    return run(r, d, op, c, a, b, batch, terms, shared, (hipStream_t)stream, comps, launch);
+    return run(r, d, op, c, a, b, batch, terms, shared, (hipStream_t)stream, comps, launch,
+               aux);
   });
 }
 
 // Host buffers: dev[0], device buffers owned by the call, the device path, copy back, synchronise
 int host_op(nttmul_rns *r, int op, void *c, const void *a, const void *b, size_t batch,
-            uint32_t terms, int shared, uint32_t comps = 1, RnsMacLaunch launch = nullptr) {
+            uint32_t terms, int shared, uint32_t comps = 1, RnsMacLaunch launch = nullptr,
+            const void *aux = nullptr) {
   if (const int st = op_args(r != nullptr, op, c, a, b, batch, terms)) return st;
   if (!batch) return NTTMUL_OK;
   RnsDev &d = r->dev[0];
@@ -167,7 +169,7 @@ int host_op(nttmul_rns *r, int op, void *c, const void *a, const void *b, size_t
                          {b, nullptr, words[2] * wb}};
   return staged_op(r->err, d.base, "rns", ops, 3, [&](void *const *buf) {
     return run(r, d, op, buf[0], buf[1], buf[2], batch, terms, shared, d.base.stream, comps,
-               launch);
+               launch, aux);
   });
 }
 
@@ -177,9 +179,10 @@ namespace nttmul {
 
 int rns_mac_comps(nttmul_rns *r, RnsMacLaunch launch, void *c, const void *a, const void *b_hat,
                   size_t batch, uint32_t terms, uint32_t comps, int shared, int host, int dev,
-                  void *stream) {
-  if (host) return host_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, comps, launch);
-  return device_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, dev, stream, comps, launch);
+                  void *stream, const void *aux) {
+  if (host) return host_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, comps, launch, aux);
+  return device_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, dev, stream, comps, launch,
+                   aux);
 }
 
 }  // namespace nttmul

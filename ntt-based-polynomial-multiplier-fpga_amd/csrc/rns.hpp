@@ -74,18 +74,23 @@ int upload_limb_tables(char *err, const std::vector<Plan> &plan, int word_bits, 
                        hipError_t (*fill)(const LaunchTables &, int, void *));
 
 
-// ---- for a sibling library that adds a mac kernel on the same context (macn.cpp) ----------------
+// ---- for a sibling library that adds a mac kernel on the same context (macn.cpp and later) ------
 
 // launch_rns's place in a call: c [batch][comps][limbs][n], b = b_hat
-// [batch or 1][comps][terms][limbs][n]
+// [batch or 1][comps][terms][limbs][n].  aux: the caller's own, passed through unread.
+// Convention for a sibling whose output has more structure than components (hoist.cpp: rots
+// rotations of comps components against one shared b_hat [rots][comps][terms][limbs][n]): it
+// passes comps = rots comps and shared = 1, so that op_words sizes c as
+// [batch][rots comps][limbs][n] and b_hat as [rots comps][terms][limbs][n] for the range check and
+// the host form, and carries the split (rots, comps, the rotations) behind aux for its launcher
 using RnsMacLaunch = hipError_t (*)(const RnsTables &T, void *c, const void *a, const void *b,
                                     size_t batch, uint32_t terms, uint32_t comps, int shared,
-                                    hipStream_t s);
+                                    hipStream_t s, const void *aux);
 // nttmul_rns_mac_ntt (host != 0; dev and stream unused) or nttmul_rns_mac_ntt_device with `comps`
 // operands per term and `launch` for the launch: the same argument checks, device selection,
 // range check (over all of b_hat) and error text
 int rns_mac_comps(nttmul_rns *r, RnsMacLaunch launch, void *c, const void *a, const void *b_hat,
                   size_t batch, uint32_t terms, uint32_t comps, int shared, int host, int dev,
-                  void *stream);
+                  void *stream, const void *aux = nullptr);
 
 }  // namespace nttmul

@@ -86,6 +86,32 @@ int ensure(nttmul_rnsmp *r, MpScratch &sc, int i, size_t need) {
   return NTTMUL_OK;
 }
 
+// A call's first use of the scratch on stream s: ordered after the last enqueued use, whatever
+// stream that was on
+int scratch_begin(nttmul_rnsmp *r, MpScratch &sc, hipStream_t s) {
+  if (!sc.ev) LIMB_TRY(r->err, hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming));
+  if (sc.used && sc.last != s) LIMB_TRY(r->err, hipStreamWaitEvent(s, sc.ev, 0));
+  return NTTMUL_OK;
+}
+
+// After a call's launches, also after a failure (what was enqueued still uses the scratch): the
+// event the next use waits for.  st: the call's status so far, returned unless it was OK
+int scratch_end(nttmul_rnsmp *r, MpScratch &sc, hipStream_t s, int st) {
+  const hipError_t e = hipEventRecord(sc.ev, s);
+  sc.used = true;
+  sc.last = s;
+  if (!st && e != hipSuccess) st = fail(r->err, e, "hipEventRecord(scratch)");
+  return st;
+}
+
+// NTTMUL_FLAG_VALIDATE: a_words of a and b_words of b against their limbs' moduli
+int validate(nttmul_rnsmp *r, MpDev &d, const void *a, size_t a_words, const void *b,
+             size_t b_words, hipStream_t s) {
+  if (!(r->flags & NTTMUL_FLAG_VALIDATE)) return NTTMUL_OK;
+  return check_range(r->err, d.base.flag, d.base.q, r->limbs, r->logn, r->word_bits, a, a_words, b,
+                     b_words, "input coefficient >= its limb's modulus", s);
+}
+
 // on d (the current device), stream s: the range check, then sub-batches of whole polynomials
 // through the scratch.  launch: a sibling's launches in launch_rnsmp's place, with comps operands
 // per term and as many output polynomials per batch entry (rnsmp.hpp rnsmp_mac_comps)
@@ -94,14 +120,9 @@ int run(nttmul_rnsmp *r, MpDev &d, int op, void *c, const void *a, const void *b
         MpMacLaunch launch = nullptr) {
   if (!batch) return NTTMUL_OK;
   const RnsTables T = view(r, d);
-  if (r->flags & NTTMUL_FLAG_VALIDATE) {
-    size_t words[3];
-    op_words(r->limbs, r->n, op, batch, terms, shared, words, comps);
-    if (const int st = check_range(r->err, d.base.flag, d.base.q, r->limbs, r->logn, r->word_bits,
-                                   a, words[1], b, words[2],
-                                   "input coefficient >= its limb's modulus", s))
-      return st;
-  }
+  size_t words[3];
+  op_words(r->limbs, r->n, op, batch, terms, shared, words, comps);
+  if (const int st = validate(r, d, a, words[1], b, words[2], s)) return st;
   // bytes of one polynomial (all limbs) in a scratch buffer, of one polynomial's a (for the mac
   // all its terms) and of its output (all components), so that no scratch buffer of a sub-batch
   // exceeds scratch_mb
@@ -109,8 +130,7 @@ int run(nttmul_rnsmp *r, MpDev &d, int op, void *c, const void *a, const void *b
   const size_t apoly = op == kRnsMac ? poly * terms : poly, cpoly = poly * comps;
   const size_t chunk = mp_chunk((size_t)r->scratch_mb << 20, apoly, cpoly, batch);
   MpScratch &sc = d.scr;
-  if (!sc.ev) LIMB_TRY(r->err, hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming));
-  if (sc.used && sc.last != s) LIMB_TRY(r->err, hipStreamWaitEvent(s, sc.ev, 0));
+  if (const int st = scratch_begin(r, sc, s)) return st;
   const bool two = op == kRnsMultiply, three = op == kRnsMultiply || op == kRnsMac;
   int st = ensure(r, sc, 0, chunk * apoly);
   if (!st && two) st = ensure(r, sc, 1, chunk * poly);
@@ -127,12 +147,7 @@ int run(nttmul_rnsmp *r, MpDev &d, int op, void *c, const void *a, const void *b
                : launch_rnsmp(T, op, cu, au, bu, u.cnt, terms, shared, sc.buf, s);
     if (e != hipSuccess) st = fail(r->err, e, "sub-batch launch");
   }
-  // (also after a failure: what was enqueued still uses the scratch)
-  const hipError_t e = hipEventRecord(sc.ev, s);
-  sc.used = true;
-  sc.last = s;
-  if (!st && e != hipSuccess) st = fail(r->err, e, "hipEventRecord(scratch)");
-  return st;
+  return scratch_end(r, sc, s, st);
 }
 
 int device_op(nttmul_rnsmp *r, int op, void *c, const void *a, const void *b, size_t batch,
@@ -170,6 +185,61 @@ int rnsmp_mac_comps(nttmul_rnsmp *r, MpMacLaunch launch, void *c, const void *a,
                     void *stream) {
   if (host) return host_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, comps, launch);
   return device_op(r, kRnsMac, c, a, b_hat, batch, terms, shared, dev, stream, comps, launch);
+}
+
+}  // namespace nttmul
+
+namespace {
+
+// rnsmp_units_op on d (the current device), stream s: the range check, then sub-batches of whole
+// output units through scr[2]
+int run_units(nttmul_rnsmp *r, MpDev &d, MpUnitsLaunch launch, const void *aux, void *c,
+              const void *a, const void *b, size_t batch, uint32_t terms, uint32_t upb,
+              uint32_t comps, hipStream_t s) {
+  if (!batch) return NTTMUL_OK;
+  const RnsTables T = view(r, d);
+  size_t words[3];
+  mp_unit_words(r->limbs, r->n, batch, terms, upb, comps, words);
+  if (const int st = validate(r, d, a, words[1], b, words[2], s)) return st;
+  const size_t poly = (size_t)r->limbs * r->n * (r->word_bits / 8);
+  const size_t cunit = poly * comps, units = batch * upb;
+  const size_t chunk = mp_unit_chunk((size_t)r->scratch_mb << 20, poly, comps, units);
+  MpScratch &sc = d.scr;
+  if (const int st = scratch_begin(r, sc, s)) return st;
+  int st = ensure(r, sc, 2, chunk * cunit);
+  if (st) return st;
+  for (size_t k = 0; k < mp_subs(units, chunk) && !st; k++) {
+    const MpSub u = mp_sub(units, chunk, k);
+    const hipError_t e =
+        launch(T, (char *)c + u.p * cunit, a, b, u.p, u.cnt, terms, aux, sc.buf, s);
+    if (e != hipSuccess) st = fail(r->err, e, "sub-batch launch");
+  }
+  return scratch_end(r, sc, s, st);
+}
+
+}  // namespace
+
+namespace nttmul {
+
+int rnsmp_units_op(nttmul_rnsmp *r, MpUnitsLaunch launch, const void *aux, void *c, const void *a,
+                   const void *b, size_t batch, uint32_t terms, uint32_t upb, uint32_t comps,
+                   int host, int dev, void *stream) {
+  if (!host)
+    return on_device(r->err, r->dev, r->ndev, dev, [&](MpDev &d) {
+      return run_units(r, d, launch, aux, c, a, b, batch, terms, upb, comps,
+                       (hipStream_t)stream);
+    });
+  if (!batch) return NTTMUL_OK;
+  MpDev &d = r->dev[0];
+  size_t words[3];
+  mp_unit_words(r->limbs, r->n, batch, terms, upb, comps, words);
+  const size_t wb = (size_t)r->word_bits / 8;
+  const Staged ops[3] = {{nullptr, c, words[0] * wb}, {a, nullptr, words[1] * wb},
+                         {b, nullptr, words[2] * wb}};
+  return staged_op(r->err, d.base, "rnsmp", ops, 3, [&](void *const *buf) {
+    return run_units(r, d, launch, aux, buf[0], buf[1], buf[2], batch, terms, upb, comps,
+                     d.base.stream);
+  });
 }
 
 }  // namespace nttmul

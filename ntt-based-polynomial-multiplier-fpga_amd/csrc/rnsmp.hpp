@@ -52,4 +52,23 @@ int rnsmp_mac_comps(nttmul_rnsmp *r, MpMacLaunch launch, void *c, const void *a,
                     size_t batch, uint32_t terms, uint32_t comps, int shared, int host, int dev,
                     void *stream);
 
+// ---- for a sibling library whose row pass reads a from caller memory (no forward column pass) ----
+
+// One sub-batch of a call whose output is `upb` units per batch entry of `comps` polynomials each:
+// the units [u0, u0 + cnt) of the batch upb units of the call, c at the sub-batch's first word
+// ([cnt][comps][limbs][n]), a and b the call's whole operands; scr[2] holds cnt comps
+// polynomials and is the only scratch buffer the call may use.  aux: the caller's own, unread
+using MpUnitsLaunch = hipError_t (*)(const RnsTables &T, void *c, const void *a, const void *b,
+                                     size_t u0, size_t cnt, uint32_t terms, const void *aux,
+                                     void *const *scr, hipStream_t s);
+// A call c [batch][upb][comps][limbs][n] = f(a [batch][terms][limbs][n],
+// b [upb][comps][terms][limbs][n]) (host != 0: host buffers; dev and stream unused) with the
+// context's device selection, range check (over all of a and of b), scratch hand-over and error
+// text.  The sub-batch is the largest count of units whose cnt comps polynomials fit scratch_mb
+// (subbatch.hpp mp_chunk with no input buffer), never less than one.  The caller has checked the
+// arguments: r, and with batch > 0 the operands, are not NULL; terms, upb, comps > 0.
+int rnsmp_units_op(nttmul_rnsmp *r, MpUnitsLaunch launch, const void *aux, void *c, const void *a,
+                   const void *b, size_t batch, uint32_t terms, uint32_t upb, uint32_t comps,
+                   int host, int dev, void *stream);
+
 }  // namespace nttmul

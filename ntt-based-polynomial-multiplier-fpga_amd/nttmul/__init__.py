@@ -1571,6 +1571,108 @@ class RnsMpMacnContext(_MacnOps, RnsMpContext):
                          _flags(validate, cyclic, share_devices), scratch_mb)
 
 
+# ---- hoisted rotations (include/nttmul_hoist.h) --------------------------------------------------
+
+HOIST_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_hoist.so")
+HOIST_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_hoist.h")
+HOIST_MAX_ROTS = GALOIS_MAX_COUNT
+
+
+def load_hoist_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_hoist.so (include/nttmul_hoist.h): the ABI and kernels of
+    libnttmul_macn.so plus the hoisted rotations.  The other loaders are unaffected."""
+    return _load_limb_library(HOIST_LIB_PATH, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn,
+                              _bind_hoist)
+
+
+def _bind_hoist(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u32p = ctypes.POINTER(u32)
+    for prefix in ("nttmul_rns", "nttmul_rnsmp"):
+        getattr(lib, f"{prefix}_hoist_ntt_device").argtypes = [vp, vp, vp, vp, u32p, u32, sz, u32,
+                                                               u32, i32, vp]
+        getattr(lib, f"{prefix}_hoist_ntt").argtypes = [vp, vp, vp, vp, u32p, u32, sz, u32, u32]
+        getattr(lib, f"{prefix}_hoist_kernel_name").argtypes = [vp, u32, ctypes.c_char_p, sz]
+
+
+def hoist_exported_symbols() -> list:
+    """Function names declared in include/nttmul_hoist.h."""
+    return _header_symbols(HOIST_HEADER_PATH, "nttmul_rns")
+
+
+class _HoistOps:
+    """What RnsHoistContext and RnsMpHoistContext add to their context:
+    c[p][r][i] = INTT(sum_t sigma_{k_r}(a_hat[p][t]) o b_hat[r][i][t]) for r < rots, i < comps,
+    with sigma_k the NTT-order permutation of GaloisContext.ntt, applied while a_hat is loaded.
+    Result (r, i) equals mac_ntt of GaloisContext.coeff(a, k_r) against b_hat[r][i] bit for bit
+    when a_hat = forward(a).
+
+    Caller memory: operands need the alignment of their word only; c must overlap neither a_hat
+    nor b_hat; a call writes exactly batch * rots * comps * limbs * n words of c and never writes
+    an input."""
+
+    def hoist_kernel_name(self, comps: int) -> str:
+        """<prefix>_hoist_kernel_name, e.g. "k_rns_hoist<Arith32P,u32,12,2>"."""
+        buf = ctypes.create_string_buffer(self._NAME_CAP)
+        st = self._c.hoist_kernel_name(self._h, comps, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def hoist_ntt_device(self, c, a_hat, b_hat, ks, batch: int, terms: int, comps: int,
+                         dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        a_hat [batch][terms][limbs][n], b_hat [len(ks)][comps][terms][limbs][n],
+        c [batch][len(ks)][comps][limbs][n]; ks: the rotations, host integers."""
+        dev = self.first_dev if dev is None else dev
+        ks = [int(k) for k in ks]
+        rots = len(ks)
+        args = self._dev_args((c, a_hat, b_hat), (batch * rots * comps, batch * terms,
+                                                  rots * comps * terms), dev)
+        karr = (ctypes.c_uint32 * max(1, rots))(*ks)
+        self._check(self._c.hoist_ntt_device(self._h, *args, karr, rots, batch, terms, comps, dev,
+                                             stream or None))
+
+    def hoist_ntt(self, a_hat, b_hat, ks) -> np.ndarray:
+        """a_hat of shape [batch, terms, limbs, n]; b_hat of shape [rots, comps, terms, limbs, n]
+        with rots = len(ks).  Returns c of shape [batch, rots, comps, limbs, n]."""
+        a_hat = self._host(a_hat, 4, "a_hat")
+        b_hat = np.ascontiguousarray(b_hat, dtype=self.io_dtype)
+        ks = [int(k) for k in ks]
+        if a_hat.shape[1] == 0:
+            raise ValueError("terms must be > 0")
+        if b_hat.ndim != 5 or b_hat.shape[-3:] != a_hat.shape[1:] or b_hat.shape[0] != len(ks):
+            raise ValueError("b_hat must have shape [len(ks), comps, terms, limbs, n]")
+        rots, comps = b_hat.shape[:2]
+        c = np.empty((a_hat.shape[0], rots, comps, self.limbs, self.n), dtype=self.io_dtype)
+        karr = (ctypes.c_uint32 * max(1, rots))(*ks)
+        self._check(self._c.hoist_ntt(self._h, c.ctypes.data, a_hat.ctypes.data,
+                                      b_hat.ctypes.data, karr, rots, a_hat.shape[0],
+                                      a_hat.shape[1], comps))
+        return c
+
+
+class RnsHoistContext(_HoistOps, RnsMacnContext):
+    """An RnsContext created through lib/libnttmul_hoist.so: every RnsMacnContext method, plus
+    hoist_ntt (include/nttmul_hoist.h), for n <= 4096."""
+
+    def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False):
+        self._open_limbs(load_hoist_library(), RnsInfo(), n, moduli, ndev, first_dev,
+                         _flags(validate, cyclic, share_devices))
+
+
+class RnsMpHoistContext(_HoistOps, RnsMpMacnContext):
+    """An RnsMpContext created through lib/libnttmul_hoist.so: every RnsMpMacnContext method, plus
+    hoist_ntt (include/nttmul_hoist.h), for n in 8192 .. 65536.  A sub-batch is a run of output
+    units (p, r) whose units * comps polynomials stay within scratch_mb."""
+
+    def __init__(self, n: int, moduli, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False, scratch_mb: int = 0):
+        self._open_limbs(load_hoist_library(), RnsMpInfo(), n, moduli, ndev, first_dev,
+                         _flags(validate, cyclic, share_devices), scratch_mb)
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
