@@ -155,7 +155,8 @@ int nttmul_last_host_path(const nttmul_ctx *ctx);
  * far (>= 0; NTTMUL_EINVAL without a context), and the last one's message in reason (cap bytes,
  * "" when none): the call that met the failure ran on the launch path instead, an out-of-memory
  * failure retries the server after 64 more eligible calls (up to 3 failures), any other failure
- * leaves the launch path for the context's lifetime. */
+ * leaves the launch path for the context's lifetime.  May be called from another thread than the
+ * one that makes the context's calls: count and message are one failure's. */
 int nttmul_server_status(const nttmul_ctx *ctx, char *reason, size_t cap);
 
 /* multiply(a, b, n, q) -> c for one polynomial; host buffers of n words.

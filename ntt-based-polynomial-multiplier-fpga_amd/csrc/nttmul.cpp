@@ -28,6 +28,9 @@
 #include "copy_pool.hpp"
 #include "launch.hpp"
 #include "nttmul.h"
+#ifdef NTTMUL_SERVER_FAILPOINTS
+#include "nttmul_diag.h"
+#endif
 #ifdef NTTMUL_MAC
 #include "mac.hpp"
 #include "nttmul_mac.h"
@@ -100,6 +103,17 @@ struct Server {
   // more eligible calls take the launch path before the server is tried again (advisor r5)
   unsigned failures = 0, cooldown = 0;
   char reason[192] = {0};
+#ifdef NTTMUL_SERVER_FAILPOINTS
+  // lib/libnttmul_diag.so only (include/nttmul_diag.h): the armed failure points, and what
+  // nttmul_diag_server_state reports beyond the fields above
+  struct {
+    bool armed;
+    unsigned skip;
+    hipError_t err;
+  } fp[NTTMUL_DIAG_SITE_COUNT] = {};
+  unsigned go = 0;                            // the go word as last posted
+  unsigned launches = 0, spin_relaunches = 0, stops = 0;
+#endif
 };
 // The resident kernel occupies its hardware queue (4 per process on the box) while it waits, so
 // work other streams place in that queue -- and a device-wide synchronize -- waits behind it.  It
@@ -166,6 +180,33 @@ void set_err(nttmul_ctx *ctx, const char *msg) {
     hipError_t _e = (expr);                         \
     if (_e != hipSuccess) return fail(ctx, _e, #expr); \
   } while (0)
+
+// HIP_TRY at a failure point of the device server (include/nttmul_diag.h): in the diagnostic
+// build an armed site's call is not made and the armed error taken as its result, once; every
+// other build compiles this to HIP_TRY.
+#ifdef NTTMUL_SERVER_FAILPOINTS
+bool failpoint_fires(Server &S, int site) {
+  auto &f = S.fp[site];
+  if (!f.armed) return false;
+  if (f.skip) {
+    f.skip--;
+    return false;
+  }
+  f.armed = false;
+  return true;
+}
+#define SERVER_TRY(ctx, S, site, expr)                                      \
+  do {                                                                      \
+    hipError_t _e = failpoint_fires(S, site) ? (S).fp[site].err : (expr);   \
+    if (_e != hipSuccess) return fail(ctx, _e, #expr);                      \
+  } while (0)
+#else  // (spelled out: through HIP_TRY the error text would hold expr with its macros expanded)
+#define SERVER_TRY(ctx, S, site, expr)                 \
+  do {                                                 \
+    hipError_t _e = (expr);                            \
+    if (_e != hipSuccess) return fail(ctx, _e, #expr); \
+  } while (0)
+#endif
 
 LaunchTables tables_for(const nttmul_ctx *ctx, const DevState &d) {
   const Plan &P = ctx->plan;
@@ -488,6 +529,9 @@ int run_host_dev(nttmul_ctx *ctx, DevState &d, const HostJob &J, size_t p0, size
 // The go word into the request half.  A BAR mapping of device memory is uncached or
 // write-combining on the host, so the fences keep a and b ahead of go and push go out at once.
 void post_go(Server &S, unsigned v) {
+#ifdef NTTMUL_SERVER_FAILPOINTS
+  S.go = v;
+#endif
   __builtin_ia32_sfence();
   __atomic_store_n(&S.req->go, v, __ATOMIC_RELEASE);
   __builtin_ia32_sfence();
@@ -498,6 +542,9 @@ int server_stop(nttmul_ctx *ctx) {
   if (!S.running) return NTTMUL_OK;
   // a stop request: a new sequence number with count 0
   post_go(S, ((++S.seq) << 8) | ServerBox::kStop);
+#ifdef NTTMUL_SERVER_FAILPOINTS
+  S.stops++;
+#endif
   S.running = false;
   const hipError_t e = hipStreamSynchronize(S.s);
   // (the stop needs no answer: a relaunched kernel starts from done = S.served, and the next
@@ -510,10 +557,18 @@ int server_launch(nttmul_ctx *ctx, DevState &d) {
   Server &S = ctx->server;
   // the kernel starts from done: the last request it must not serve again (no kernel runs now)
   __atomic_store_n(&S.box->done, S.served, __ATOMIC_RELEASE);
+  // ... and serves whatever go word differs from it: a request given up unanswered (its relaunch
+  // refused, a stream error) is taken back here, or the kernel would serve it beside the next
+  // one.  Whenever no request is in flight, go == served; the spin loop posts its request again.
+  post_go(S, S.served);
   DeviceGuard guard;
   HIP_TRY(ctx, hipSetDevice(d.id));
-  HIP_TRY(ctx, launch_server(tables_for(ctx, d), S.dreq, S.dbox, kServerIdleTicks,
-                             kServerLifeTicks, S.s));
+  SERVER_TRY(ctx, S, NTTMUL_DIAG_SITE_LAUNCH,
+             launch_server(tables_for(ctx, d), S.dreq, S.dbox, kServerIdleTicks, kServerLifeTicks,
+                           S.s));
+#ifdef NTTMUL_SERVER_FAILPOINTS
+  S.launches++;
+#endif
   S.running = true;
   S.launched = S.last_done = std::chrono::steady_clock::now();
   return NTTMUL_OK;
@@ -522,16 +577,19 @@ int server_launch(nttmul_ctx *ctx, DevState &d) {
 // The mailbox (launch.hpp ServerReq / ServerBox).  The request half goes to fine-grained device
 // memory when the runtime gives the host a mapping of it (large BAR) and a probe written through
 // that mapping reads back through the device; otherwise to pinned host memory.
-int server_alloc(nttmul_ctx *ctx, DevState &d) {
+int server_alloc_try(nttmul_ctx *ctx, DevState &d) {
   Server &S = ctx->server;
-  DeviceGuard guard;
   HIP_TRY(ctx, hipSetDevice(d.id));
   if (!S.box) {
-    HIP_TRY(ctx, hipHostMalloc((void **)&S.box, sizeof(ServerBox), hipHostMallocCoherent));
+    SERVER_TRY(ctx, S, NTTMUL_DIAG_SITE_BOX_ALLOC,
+               hipHostMalloc((void **)&S.box, sizeof(ServerBox), hipHostMallocCoherent));
     memset((void *)S.box, 0, sizeof(ServerBox));
-    HIP_TRY(ctx, hipHostGetDevicePointer((void **)&S.dbox, S.box, 0));
+    SERVER_TRY(ctx, S, NTTMUL_DIAG_SITE_BOX_MAP,
+               hipHostGetDevicePointer((void **)&S.dbox, S.box, 0));
   }
-  if (!S.s) HIP_TRY(ctx, hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
+  if (!S.s)
+    SERVER_TRY(ctx, S, NTTMUL_DIAG_SITE_STREAM,
+               hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
   void *dv = nullptr;
   if (hipExtMallocWithFlags(&dv, sizeof(ServerReq), hipDeviceMallocFinegrained) == hipSuccess) {
     hsa_amd_pointer_info_t info;
@@ -560,11 +618,36 @@ int server_alloc(nttmul_ctx *ctx, DevState &d) {
   }
   (void)hipGetLastError();
   if (!S.req) {
-    HIP_TRY(ctx, hipHostMalloc((void **)&S.req, sizeof(ServerReq), hipHostMallocCoherent));
-    HIP_TRY(ctx, hipHostGetDevicePointer((void **)&S.dreq, S.req, 0));
+    SERVER_TRY(ctx, S, NTTMUL_DIAG_SITE_REQ_ALLOC,
+               hipHostMalloc((void **)&S.req, sizeof(ServerReq), hipHostMallocCoherent));
+    SERVER_TRY(ctx, S, NTTMUL_DIAG_SITE_REQ_MAP,
+               hipHostGetDevicePointer((void **)&S.dreq, S.req, 0));
   }
   post_go(S, 0);
   return NTTMUL_OK;
+}
+
+// Both halves of the mailbox, freed and forgotten (no kernel runs).
+void server_free_mailbox(Server &S) {
+  if (S.box) (void)hipHostFree(S.box);
+  if (S.req_in_vram)
+    (void)hipFree(S.dreq);
+  else if (S.req)
+    (void)hipHostFree(S.req);
+  S.box = S.dbox = nullptr;
+  S.req = S.dreq = nullptr;
+  S.req_in_vram = false;
+}
+
+// A setup that fails half-way leaves nothing behind: with a host pointer kept and its device
+// pointer missing, the retry (run_server: !S.req) would skip the allocation and launch the kernel
+// on a null mailbox.  (The stream, if it was created, stays for the retry.)
+int server_alloc(nttmul_ctx *ctx, DevState &d) {
+  Server &S = ctx->server;
+  DeviceGuard guard;
+  const int st = server_alloc_try(ctx, d);
+  if (st) server_free_mailbox(S);
+  return st;
 }
 
 // The context's server leaves before the context enqueues anything else (run_device, the launch
@@ -647,6 +730,11 @@ int run_server(nttmul_ctx *ctx, void *c, const void *a, const void *b, size_t ba
   memcpy(S.req->a, a, words * 4);
   memcpy(S.req->b, b, words * 4);
   const unsigned seq = ((++S.seq) << 8) | (unsigned)batch;  // batch <= 4: one go word
+#ifdef NTTMUL_SERVER_FAILPOINTS
+  // the kernel leaves through its idle exit while the host still takes it as running
+  if (failpoint_fires(S, NTTMUL_DIAG_SITE_STALL_BEFORE_GO))
+    std::this_thread::sleep_for(std::chrono::microseconds(3 * kServerIdleTicks / 100));
+#endif
   const auto t0 = std::chrono::steady_clock::now();
   post_go(S, seq);
   const auto landed = [&]() {
@@ -667,11 +755,17 @@ int run_server(nttmul_ctx *ctx, void *c, const void *a, const void *b, size_t ba
       // this request after the check above, or it left before it saw it -- then relaunch
       if (landed()) break;
       S.running = false;
-      // (a relaunch the runtime refuses: this request takes the launch path)
-      const int st = server_launch(ctx, d);
-      if (st) return server_unavailable(ctx, st);
+      // (a relaunch the runtime refuses: this request takes the launch path, and server_launch
+      // has taken its go word back)
+      const int rst = server_launch(ctx, d);
+      if (rst) return server_unavailable(ctx, rst);
+#ifdef NTTMUL_SERVER_FAILPOINTS
+      S.spin_relaunches++;
+#endif
+      post_go(S, seq);  // the request again, to the new kernel
     } else if (q != hipErrorNotReady) {
       S.running = false;
+      post_go(S, S.served);  // (given up unanswered: taken back, as in server_launch)
       return fail(ctx, q, "device server");
     }
     if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
@@ -869,11 +963,7 @@ void nttmul_destroy(nttmul_ctx *ctx) {
     (void)hipSetDevice(ctx->dev[0].id);
     (void)server_stop(ctx);
     if (S.s) (void)hipStreamDestroy(S.s);
-    if (S.box) (void)hipHostFree(S.box);
-    if (S.req_in_vram)
-      (void)hipFree(S.dreq);
-    else if (S.req)
-      (void)hipHostFree(S.req);
+    server_free_mailbox(S);
   }
   for (int i = 0; i < ctx->ndev; i++) {
     DevState &d = ctx->dev[i];
@@ -919,6 +1009,9 @@ int nttmul_last_host_path(const nttmul_ctx *ctx) { return ctx ? ctx->last_path :
 
 int nttmul_server_status(const nttmul_ctx *ctx, char *reason, size_t cap) {
   if (!ctx) return NTTMUL_EINVAL;
+  // (server_unavailable writes the reason under this lock: a reader on another thread gets one
+  // failure's count and text, never half of each)
+  std::lock_guard<std::mutex> l(g_err_mu);
   if (reason && cap) snprintf(reason, cap, "%s", ctx->server.reason);
   return (int)ctx->server.failures;
 }
@@ -1223,6 +1316,39 @@ int nttmul_diag_server_stamps(const nttmul_ctx *ctx, uint64_t *dst) {
   if (!ctx->server.box || ctx->last_path != 3) return NTTMUL_EINVAL;
   for (int k = 0; k < 6; k++) dst[k] = __atomic_load_n(&ctx->server.box->stamp[k], __ATOMIC_ACQUIRE);
   dst[6] = ctx->server.host_ns;
+  return NTTMUL_OK;
+}
+#endif
+
+#ifdef NTTMUL_SERVER_FAILPOINTS
+// include/nttmul_diag.h (lib/libnttmul_diag.so only)
+int nttmul_diag_server_failpoint(nttmul_ctx *ctx, int site, int hip_error, unsigned skip) {
+  if (!ctx || site < 0 || site >= NTTMUL_DIAG_SITE_COUNT) return NTTMUL_EINVAL;
+  if (site != NTTMUL_DIAG_SITE_STALL_BEFORE_GO && hip_error == (int)hipSuccess) return NTTMUL_EINVAL;
+  auto &f = ctx->server.fp[site];
+  f.armed = true;
+  f.skip = skip;
+  f.err = (hipError_t)hip_error;
+  return NTTMUL_OK;
+}
+int nttmul_diag_server_state(const nttmul_ctx *ctx, nttmul_diag_server_state_t *out) {
+  if (!ctx || !out) return NTTMUL_EINVAL;
+  const Server &S = ctx->server;
+  memset(out, 0, sizeof(*out));
+  out->go = S.go;
+  out->done = S.box ? __atomic_load_n(&S.box->done, __ATOMIC_ACQUIRE) : 0;
+  out->served = S.served;
+  out->seq = S.seq;
+  out->running = S.running;
+  out->cooldown = S.cooldown;
+  out->failures = S.failures;
+  out->small_server = ctx->small_server;
+  out->box_pair = (S.box ? 1 : 0) + (S.dbox ? 1 : 0);
+  out->req_pair = (S.req ? 1 : 0) + (S.dreq ? 1 : 0);
+  out->req_in_vram = S.req_in_vram;
+  out->launches = S.launches;
+  out->spin_relaunches = S.spin_relaunches;
+  out->stops = S.stops;
   return NTTMUL_OK;
 }
 #endif

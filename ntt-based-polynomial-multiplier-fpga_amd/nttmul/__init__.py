@@ -77,6 +77,23 @@ class Info(ctypes.Structure):
                 ("ndev", ctypes.c_int), ("kernel", ctypes.c_int), ("cyclic", ctypes.c_uint32)]
 
 
+# include/nttmul_diag.h: the device server's failure points (nttmul_diag_server_failpoint sites)
+DIAG_SITES = ("BOX_ALLOC", "BOX_MAP", "STREAM", "REQ_ALLOC", "REQ_MAP", "LAUNCH", "STALL_BEFORE_GO")
+# hipError_t values an armed site returns: the one fail() maps to NTTMUL_ENOMEM, and another
+HIP_ERROR_OUT_OF_MEMORY = 2
+HIP_ERROR_INVALID_VALUE = 1
+
+
+class DiagServerState(ctypes.Structure):
+    """include/nttmul_diag.h nttmul_diag_server_state_t."""
+    _fields_ = [("go", ctypes.c_uint32), ("done", ctypes.c_uint32), ("served", ctypes.c_uint32),
+                ("seq", ctypes.c_uint32), ("running", ctypes.c_int32), ("cooldown", ctypes.c_uint32),
+                ("failures", ctypes.c_uint32), ("small_server", ctypes.c_int32),
+                ("box_pair", ctypes.c_int32), ("req_pair", ctypes.c_int32),
+                ("req_in_vram", ctypes.c_int32), ("launches", ctypes.c_uint32),
+                ("spin_relaunches", ctypes.c_uint32), ("stops", ctypes.c_uint32)]
+
+
 _LIB: Optional[ctypes.CDLL] = None
 _DIAG_LIB: Optional[ctypes.CDLL] = None
 
@@ -94,7 +111,9 @@ def load_library() -> ctypes.CDLL:
 
 def load_diag_library() -> ctypes.CDLL:
     """Load lib/libnttmul_diag.so (include/nttmul_diag.h): the same ABI, kernels with in-kernel
-    clock stamps; used by bench.py for the clock the product kernel holds, never for results."""
+    clock stamps; used by bench.py for the clock the product kernel holds, never for results.
+    It also holds the device server's failure points and state read-out (diag_server_failpoint,
+    diag_server_state), for the tests of the server's failure and retry paths."""
     global _DIAG_LIB
     if _DIAG_LIB is not None:
         return _DIAG_LIB
@@ -102,6 +121,9 @@ def load_diag_library() -> ctypes.CDLL:
         raise ImportError(f"{DIAG_LIB_PATH} not built")
     lib = _bind(ctypes.CDLL(DIAG_LIB_PATH))
     lib.nttmul_diag_clock_stamps.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    lib.nttmul_diag_server_failpoint.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_uint]
+    lib.nttmul_diag_server_state.argtypes = [ctypes.c_void_p, ctypes.POINTER(DiagServerState)]
     _DIAG_LIB = lib
     return lib
 
@@ -518,6 +540,19 @@ class Context:
         if n < 0:
             self._check(n)
         return int(n), buf.value.decode()
+
+    def diag_server_failpoint(self, site: str, hip_error: int = HIP_ERROR_OUT_OF_MEMORY,
+                              skip: int = 0) -> None:
+        """nttmul_diag_server_failpoint (a context of load_diag_library() only): arm `site`, one
+        of DIAG_SITES, to fail once with hip_error after `skip` further passes."""
+        self._check(self._lib.nttmul_diag_server_failpoint(self._h, DIAG_SITES.index(site),
+                                                           hip_error, skip))
+
+    def diag_server_state(self) -> dict:
+        """nttmul_diag_server_state (a context of load_diag_library() only), as a dict."""
+        st = DiagServerState()
+        self._check(self._lib.nttmul_diag_server_state(self._h, ctypes.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in DiagServerState._fields_}
 
     def kernel_name(self, word_bits: int = 0, batch: int = 0) -> str:
         """The device kernel(s) a product call of `batch` polynomials dispatches to

@@ -17,9 +17,16 @@ Three things live here:
   the (sequence, step index) pairs that drive it.  `drives(transition, ctx, state, step)` is the
   pure predicate over (state before, step) behind each row.
 
+`SERVER_SEQUENCES` are the sequences over the resident server's failure and retry paths: their
+steps arm failure points of the diagnostic library (include/nttmul_diag.h), and the model's
+"server" entry carries the failure count, the cool-down, the permanent switch to the launch path
+and whether the go word equals the last one served.  tests/test_gpu_server_failures.py runs them.
+
 tests/test_lifetime_ledger.py holds the table against the source and the model without a GPU.
 """
 import copy
+import os
+import re
 from collections import namedtuple
 
 import dispatch_cases as D
@@ -31,7 +38,28 @@ ZERO_COPY = 64 << 10            # nttmul_params.zero_copy_kb default
 SERVER_WORDS = 1024             # launch.hpp ServerBox::kWords
 PATHS = ("staged", "direct", "zero_copy", "server")     # nttmul_last_host_path 0, 1, 2, 3
 
-# lib: "plain" (nttmul.Context) or "mac" (nttmul.MacContext)
+SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                      "ntt-based-polynomial-multiplier-fpga_amd", "csrc", "nttmul.cpp")
+
+
+def _server_constants():
+    """kServerRetryCalls and kServerMaxFailures as nttmul.cpp states them."""
+    m = re.findall(r"constexpr unsigned kServerRetryCalls = (\d+), kServerMaxFailures = (\d+);",
+                   open(SOURCE).read())
+    assert len(m) == 1, m
+    return int(m[0][0]), int(m[0][1])
+
+
+RETRY_CALLS, MAX_FAILURES = _server_constants()
+# include/nttmul_diag.h: the failure points in the order server_alloc passes them, then the launch
+ALLOC_SITES = ("BOX_ALLOC", "BOX_MAP", "STREAM", "REQ_ALLOC", "REQ_MAP")
+SITES = ALLOC_SITES + ("LAUNCH", "STALL_BEFORE_GO")
+# the error an armed site returns: hipErrorOutOfMemory (fail() maps it to NTTMUL_ENOMEM, the
+# status server_unavailable retries) or hipErrorInvalidValue (NTTMUL_EHIP: no retry)
+ENOMEM, EINVAL = "ENOMEM", "EINVAL"
+
+# lib: "plain" (nttmul.Context), "mac" (nttmul.MacContext) or "diag" (nttmul.Context on
+#   nttmul.load_diag_library(): the failure points of SERVER_SEQUENCES)
 Ctx = namedtuple("Ctx", "n q lib scratch_mb validate ndev share_devices",
                  defaults=("plain", 0, False, 1, False))
 
@@ -41,8 +69,10 @@ Ctx = namedtuple("Ctx", "n q lib scratch_mb validate ndev share_devices",
 # place: device operands on caller stream "A", "B" or the "null" stream; "host" (pageable) or
 #   "pinned" (nttmul.host_empty) host arrays
 # status: "OK", or "ERANGE" on a validating context: polynomial `bad` of a holds one coefficient q
-Step = namedtuple("Step", "entry place bits batch mode status terms bad",
-                  defaults=(0, "OK", 0, None))
+# arm: failure points armed before the call, (site, error, skip) each: after `skip` further passes
+#   the site's runtime call is not made and returns `error` (STALL_BEFORE_GO: error None)
+Step = namedtuple("Step", "entry place bits batch mode status terms bad arm",
+                  defaults=(0, "OK", 0, None, ()))
 
 HOST_PLACES = ("host", "pinned")
 
@@ -167,6 +197,85 @@ SEQUENCES = {"A": SEQ_A, "B": SEQ_B, "C": SEQ_C, "D": SEQ_D, "E": SEQ_E, "F_host
              "F_device": SEQ_F_DEVICE, "F_sub": SEQ_F_SUB, "F_server": SEQ_F_SERVER, "G": SEQ_G,
              "H": SEQ_H}
 
+
+# ---------------------------------------------------------------------------------------------
+# The resident server's failure and retry paths (diagnostic library)
+# ---------------------------------------------------------------------------------------------
+
+STALL = ("STALL_BEFORE_GO", None, 0)
+
+
+def _cool(first=0, n=None, top=4):
+    """kServerRetryCalls eligible calls (the cool-down), batches 1 .. top in turn."""
+    return [_h("multiply", 1 + (first + i) % top) for i in range(RETRY_CALLS if n is None else n)]
+
+
+# S1. the kernel has left through its idle exit while a request waits: relaunched inside the spin
+# loop, served; then smaller requests over the larger one's words in box->c
+SEQ_S1 = (Ctx(256, Q31HI, lib="diag"), [
+    _h("multiply", 4),                          # 0 first launch
+    _h("multiply", 4, arm=(STALL,)),            # 1 relaunch in the spin loop
+    _h("multiply", 1),                          # 2 one product: 768 older words stay in box->c
+    _h("multiply", 2, arm=(STALL,)),            # 3
+    _h("multiply", 3),                          # 4
+])
+
+
+def _s2(n, big):
+    """S2. a relaunch refused in the middle of a request, the cool-down, the retry.  Step 1 leaves
+    the server stopped, so step 2 launches once on entry whatever the time since step 0 (the host's
+    idle margin would otherwise decide) and LAUNCH with skip 1 is the relaunch in the spin loop."""
+    cool = _cool(1, top=big)
+    cool.insert(20, _h("multiply", 1, status="ERANGE", bad=0))      # neither consumes cool-down
+    cool.insert(41, _h("pointwise", 2))
+    return (Ctx(n, Q31HI, lib="diag", validate=True), [
+        _h("multiply", big),                    # 0 served
+        _h("pointwise", 1),                     # 1 never the server's: quiesces it
+        _h("multiply", max(1, big // 2), arm=(("LAUNCH", ENOMEM, 1), STALL)),   # 2 refused
+    ] + cool + [
+        _h("multiply", 1),                      # served again: the retry
+        _h("multiply", big),
+    ])
+
+
+SEQ_S2 = _s2(256, 4)
+SEQ_S2_512 = _s2(512, 1)
+SEQ_S2_1024 = _s2(1024, 1)
+
+# S3. the cap: the third out-of-memory failure leaves the launch path for good
+SEQ_S3 = (Ctx(256, Q31HI, lib="diag"),
+          [_h("multiply", 2, arm=(("LAUNCH", ENOMEM, 0),))] + _cool(0)
+          + [_h("multiply", 3, arm=(("LAUNCH", ENOMEM, 0),))] + _cool(1)
+          + [_h("multiply", 4, arm=(("LAUNCH", ENOMEM, 0),))] + _cool(2, 10))
+
+# S4. a failure that is not out of memory: permanent at once
+SEQ_S4 = (Ctx(256, Q31HI, lib="diag"),
+          [_h("multiply", 3, arm=(("LAUNCH", EINVAL, 0),))] + _cool(0, 6))
+
+
+def _s5(site):
+    """S5. a setup that fails half-way: nothing is left behind, and the retry allocates again."""
+    return (Ctx(256, Q31HI, lib="diag"),
+            [_h("multiply", 4, arm=((site, ENOMEM, 0),))] + _cool(0)
+            + [_h("multiply", 2), _h("multiply", 4)])
+
+
+# S6. nttmul_destroy on a context in cool-down and on a permanently switched one (the test then
+# serves on a fresh context: sequence S6_fresh)
+SEQ_S6_COOL = (Ctx(256, Q31HI, lib="diag"),
+               [_h("multiply", 4),
+                _h("pointwise", 1),
+                _h("multiply", 2, arm=(("LAUNCH", ENOMEM, 1), STALL))] + _cool(0, 3))
+SEQ_S6_OFF = (Ctx(256, Q31HI, lib="diag"),
+              [_h("multiply", 1, arm=(("BOX_MAP", EINVAL, 0),))] + _cool(0, 3))
+SEQ_S6_FRESH = (Ctx(256, Q31HI, lib="diag"), [_h("multiply", 4), _h("multiply", 1)])
+
+SERVER_SEQUENCES = {"S1": SEQ_S1, "S2": SEQ_S2, "S2_512": SEQ_S2_512, "S2_1024": SEQ_S2_1024,
+                    "S3": SEQ_S3, "S4": SEQ_S4,
+                    **{"S5_" + site.lower(): _s5(site) for site in ALLOC_SITES},
+                    "S6_cool": SEQ_S6_COOL, "S6_off": SEQ_S6_OFF, "S6_fresh": SEQ_S6_FRESH}
+ALL_SEQUENCES = {**SEQUENCES, **SERVER_SEQUENCES}
+
 # I. one caller stream through the four libraries (no per-context state to model: the stages are
 # listed in tests/test_gpu_lifetime.py); n, batch, terms
 CHAIN = (1024, 3, 2)
@@ -183,9 +292,16 @@ def _scratch():
 
 
 def new_state(cp):
-    """A context after nttmul_create."""
+    """A context after nttmul_create.  server: running, launches and served as the host counts
+    them; failures, cooldown, disabled (small_server == -1) and reason = (failure number, status
+    name, retried, site) of server_unavailable; go_is_served: req->go == S.served, which holds whenever
+    no request is in flight; allocated / stream: the mailbox and the stream exist; spin and stops:
+    relaunches inside the spin loop and stop requests; armed: site -> [error, passes to skip]."""
     return {"last_path": -1, "failed": False, "last_prod": None,
-            "server": {"running": False, "launches": 0, "served": 0},
+            "server": {"running": False, "launches": 0, "served": 0, "failures": 0, "cooldown": 0,
+                       "disabled": False, "reason": None, "go_is_served": True,
+                       "allocated": False, "stream": False, "spin": 0, "stops": 0, "armed": {},
+                       "last_batch": 0},
             "dev": [{"slot_bytes": 0, "slot_bits": 0, "slot_op": None, "prod_s": None, "dscr": _scratch(),
                      "sscr": [_scratch() for _ in range(SLOTS)]} for _ in range(cp.ndev)]}
 
@@ -202,10 +318,11 @@ def zero_copy_chunk(cp, nbytes):
     return nbytes <= ZERO_COPY and cp.n <= 4096
 
 
-def host_path(cp, step):
-    """The nttmul_last_host_path number a host step reports (run_host / run_server)."""
+def host_path(cp, step, server=True):
+    """The nttmul_last_host_path number a host step reports (run_host / run_server; server=False:
+    run_server has declined the call)."""
     assert step.place in HOST_PLACES
-    if server_takes(cp, step):
+    if server and server_takes(cp, step):
         return 3
     pbytes = cp.n * step.bits // 8
     chunk = max(1, CHUNK_BYTES // pbytes)
@@ -222,9 +339,11 @@ def slices(cp, batch):
 Walk = namedtuple("Walk", "state tags cases path")
 
 
-def walk(cp, before, step):
+def walk(cp, before, step, in_vram=True):
     """One call on a context in state `before`: Walk(state after, transition names driven, the
-    launches as Case rows, the host path reported or None for a device call)."""
+    launches as Case rows, the host path reported or None for a device call).  in_vram: the
+    request half of the mailbox goes to fine-grained device memory (server_alloc then never
+    reaches REQ_ALLOC and REQ_MAP); the GPU test passes what the machine did."""
     st = copy.deepcopy(before)
     tags, cases = set(), []
     n, q, bits = cp.n, cp.q, step.bits
@@ -240,6 +359,85 @@ def walk(cp, before, step):
         if S["running"]:
             tags.update(("server.quiesce", "server.quiesce." + site))
             S["running"] = False
+            S["stops"] += 1
+
+    for site, error, skip in step.arm:
+        assert site in SITES and (error is None) == (site == "STALL_BEFORE_GO")
+        assert cp.lib == "diag"
+        S["armed"][site] = [error, skip]
+
+    def fires(site):
+        """failpoint_fires: the armed error (True for the stall) once `skip` passes are through."""
+        f = S["armed"].get(site)
+        if f is None:
+            return None
+        if f[1]:
+            f[1] -= 1
+            return None
+        del S["armed"][site]
+        return f[0] or True
+
+    def unavailable(kind, error, site):
+        """server_unavailable after fail() at `site`: this call takes the launch path."""
+        status = "ENOMEM" if error == ENOMEM else "EHIP"
+        S["running"] = False
+        S["failures"] += 1
+        retry = status == "ENOMEM" and S["failures"] < MAX_FAILURES
+        tags.update(("server.unavailable." + kind, "server.status_locked"))
+        if retry:
+            tags.add("server.retry_armed")
+            S["cooldown"] = RETRY_CALLS
+        else:
+            tags.add("server.permanent.cap" if status == "ENOMEM" else "server.permanent.other")
+            S["disabled"] = True
+        S["reason"] = (S["failures"], status, retry, site)
+        return False
+
+    def serve():
+        """run_server past its eligibility and range checks; False: the launch path."""
+        if S["cooldown"]:
+            tags.add("server.cooldown")
+            S["cooldown"] -= 1
+            return False
+        first = not S["allocated"]
+        if first:
+            for site in ALLOC_SITES:
+                if site == "STREAM" and S["stream"]:
+                    continue
+                if site in ("REQ_ALLOC", "REQ_MAP") and in_vram:
+                    continue
+                error = fires(site)
+                if error:
+                    tags.add("server.alloc_rollback")
+                    return unavailable("alloc", error, site)
+                if site == "STREAM":
+                    S["stream"] = True
+            S["allocated"] = True
+        if S["running"]:
+            tags.add("server.resident")
+        else:
+            tags.add("server.launch_first" if first else "server.relaunch")
+            error = fires("LAUNCH")
+            if error:
+                return unavailable("launch", error, "LAUNCH")
+            S["launches"] += 1
+            S["running"] = True
+        if fires("STALL_BEFORE_GO"):
+            # the kernel has left; the request is posted, found unanswered and the kernel finished
+            tags.add("server.spin_relaunch")
+            S["go_is_served"] = False
+            error = fires("LAUNCH")
+            S["go_is_served"] = True            # server_launch takes the go word back first
+            if error:
+                tags.add("server.take_back")
+                return unavailable("relaunch", error, "LAUNCH")
+            S["launches"] += 1
+            S["spin"] += 1
+        if S["served"]:
+            tags.add("server.served_advance")
+        S["served"] += 1
+        S["last_batch"] = step.batch
+        return True
 
     def done(path=None):
         if not erange:
@@ -327,27 +525,21 @@ def walk(cp, before, step):
             st["failed"] = True
         return done()
 
-    if server_takes(cp, step):
+    served = False
+    if server_takes(cp, step) and not S["disabled"]:
         if erange:                          # the range check of run_server, on the host
             tags.add("server.erange")
             st["failed"] = True
             return done(None)
+        served = serve()
+    if served:
         if st["failed"] and cp.validate:
             tags.add("server.after_erange")
-        if S["running"]:
-            tags.add("server.resident")
-        else:
-            tags.add("server.relaunch" if S["launches"] else "server.launch_first")
-            S["launches"] += 1
-            S["running"] = True
-        if S["served"]:
-            tags.add("server.served_advance")
-        S["served"] += 1
         cases.append(Case("multiply", n, q, 32, step.batch, path="server"))
         path = 3
     else:
         quiesce("run_host")
-        path = host_path(cp, step)
+        path = host_path(cp, step, server=False)
         direct = path == 1
         chunk = max(1, CHUNK_BYTES // io_poly)
         for i, (p0, p1) in enumerate(slices(cp, step.batch)):
@@ -391,30 +583,30 @@ def walk(cp, before, step):
     return done(path)
 
 
-def model(name):
+def model(name, in_vram=True):
     """[Walk] of a sequence, one per step, from a fresh context."""
-    cp, steps = SEQUENCES[name]
+    cp, steps = ALL_SEQUENCES[name]
     st, out = new_state(cp), []
     for step in steps:
-        out.append(walk(cp, st, step))
+        out.append(walk(cp, st, step, in_vram))
         st = out[-1].state
     return out
 
 
-def state_before(name, index):
-    cp, _ = SEQUENCES[name]
-    return new_state(cp) if index == 0 else model(name)[index - 1].state
+def state_before(name, index, in_vram=True):
+    cp, _ = ALL_SEQUENCES[name]
+    return new_state(cp) if index == 0 else model(name, in_vram)[index - 1].state
 
 
-def drives(transition, cp, before, step):
+def drives(transition, cp, before, step, in_vram=True):
     """The predicate of a transition over (state before, step)."""
-    return transition in walk(cp, before, step).tags
+    return transition in walk(cp, before, step, in_vram).tags
 
 
 def lifetime_cases():
     """Every launch the sequences make, as dispatch_cases.Case rows (each distinct row once)."""
     out = []
-    for name in SEQUENCES:
+    for name in ALL_SEQUENCES:
         for w in model(name):
             for c in w.cases:
                 if c not in out:
@@ -504,7 +696,31 @@ TRANSITIONS = (
     T("server.quiesce.fill", "int nttmul_fill_random_device(", r"server_quiesce\(ctx\)", (("A", 16),)),
     T("server.quiesce.mac_device", "int nttmul_mac_ntt_device(", r"server_quiesce\(ctx\)", (("H", 1),)),
     T("server.quiesce.mac_host", "static int mac_host(", r"server_quiesce\(ctx\)", (("H", 3),)),
-    T("server.erange", "int run_server(", r"if \(pa\[i\] >= P\.q \|\| pb\[i\] >= P\.q\) \{", (("F_server", 1),)),
+    # ... its failure and retry paths (SERVER_SEQUENCES)
+    T("server.cooldown", "int run_server(", r"S\.cooldown--;", (("S2", 3), ("S3", 1), ("S5_box_map", 64))),
+    T("server.unavailable.alloc", "int run_server(", r"const int st = server_alloc\(ctx, d\);",
+      (("S5_box_alloc", 0), ("S5_box_map", 0), ("S5_stream", 0), ("S6_off", 0))),
+    T("server.unavailable.launch", "int run_server(", r"const int st = server_launch\(ctx, d\);",
+      (("S3", 0), ("S3", RETRY_CALLS + 1), ("S3", 2 * RETRY_CALLS + 2), ("S4", 0))),
+    T("server.unavailable.relaunch", "int run_server(", r"if \(rst\) return server_unavailable\(ctx, rst\);",
+      (("S2", 2), ("S2_512", 2), ("S2_1024", 2), ("S6_cool", 2))),
+    T("server.retry_armed", "int server_unavailable(", r"S\.cooldown = kServerRetryCalls;",
+      (("S2", 2), ("S3", 0), ("S3", RETRY_CALLS + 1), ("S5_box_map", 0))),
+    T("server.permanent.cap", "int server_unavailable(",
+      r"const bool retry = st == NTTMUL_ENOMEM && S\.failures < kServerMaxFailures;",
+      (("S3", 2 * RETRY_CALLS + 2),)),
+    T("server.permanent.other", "int server_unavailable(", r"ctx->small_server = -1;",
+      (("S4", 0), ("S6_off", 0))),
+    T("server.spin_relaunch", "int run_server(", r"const int rst = server_launch\(ctx, d\);",
+      (("S1", 1), ("S1", 3), ("S2", 2), ("S6_cool", 2))),
+    T("server.take_back", "int server_launch(", r"post_go\(S, S\.served\);",
+      (("S2", 2), ("S2_512", 2), ("S2_1024", 2), ("S6_cool", 2))),
+    T("server.alloc_rollback", "int server_alloc(", r"if \(st\) server_free_mailbox\(S\);",
+      (("S5_box_alloc", 0), ("S5_box_map", 0), ("S5_stream", 0), ("S6_off", 0))),
+    T("server.status_locked", "int nttmul_server_status(", r"std::lock_guard<std::mutex> l\(g_err_mu\);",
+      (("S2", 2), ("S3", 0), ("S4", 0), ("S5_box_map", 0))),
+    T("server.erange", "int run_server(", r"if \(pa\[i\] >= P\.q \|\| pb\[i\] >= P\.q\) \{",
+      (("F_server", 1), ("S2", 23))),
     T("server.after_erange", "int run_server(", r"for \(size_t i = 0; i < words; i\+\+\) bc\[i\] = ServerBox::kPending;",
       (("F_server", 2),)),
     # prod_s, last_prod, d.flag, err
@@ -530,4 +746,13 @@ TRANSITIONS = (
     # libnttmul_mac.so's calls on the same context
     T("mac.device", "static int mac_run(", r"launch_mac\(tables_for\(ctx, d\), a, b_hat, c, batch, terms", (("H", 1),)),
     T("mac.host", "static int mac_host(", r"const hipError_t e = hipStreamSynchronize\(d\.stream\);", (("H", 3),)),
+)
+
+# Paths of run_server that no sequence drives, with the line each would pin and the reason.
+EXEMPT = (
+    T("server.query_error", "int run_server(", r"return fail\(ctx, q, \"device server\"\);",
+      "a real error of hipStreamQuery means the device is gone, and a staged one leaves a live "
+      "kernel the host has disowned"),
+    T("server.timeout", "int run_server(", r"set_err\(ctx, \"device server: no answer within 5 s\"\);",
+      "needs a resident kernel that hangs for 5 s"),
 )

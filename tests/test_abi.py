@@ -37,9 +37,37 @@ def test_diag_library_exports_both_headers():
     names = {line.split()[-1] for line in out.splitlines() if " T " in line}
     diag_h = os.path.join(os.path.dirname(nttmul.HEADER_PATH), "nttmul_diag.h")
     diag = set(re.findall(r"^int (nttmul_diag_\w+)\(", open(diag_h).read(), re.M))
-    assert diag == {"nttmul_diag_clock_stamps", "nttmul_diag_server_stamps"}, diag
+    assert diag == {"nttmul_diag_clock_stamps", "nttmul_diag_server_stamps",
+                    "nttmul_diag_server_failpoint", "nttmul_diag_server_state"}, diag
     missing = (set(nttmul.exported_symbols()) | diag) - names
     assert not missing, missing
+    assert {n for n in names if n.startswith("nttmul_diag_")} == diag
+
+
+def test_only_the_diag_library_holds_the_diagnostic_entry_points():
+    """The failure points of the device server (include/nttmul_diag.h) exist in the diagnostic
+    build alone: no other library under lib/ defines a nttmul_diag_* symbol, and the Python
+    bindings of the two new entry points match the header's site list and state structure."""
+    import glob
+    import re
+    libs = sorted(glob.glob(os.path.join(os.path.dirname(nttmul.LIB_PATH), "*.so")))
+    assert nttmul.LIB_PATH in libs
+    for path in libs:
+        if os.path.basename(path) == "libnttmul_diag.so":
+            continue
+        out = subprocess.run(["nm", "-D", path], capture_output=True, text=True, check=True).stdout
+        assert "nttmul_diag_" not in out, path
+    hdr = open(os.path.join(os.path.dirname(nttmul.HEADER_PATH), "nttmul_diag.h")).read()
+    sites = re.findall(r"NTTMUL_DIAG_SITE_(\w+) = (\d+)", hdr)
+    assert [(nm, int(v)) for nm, v in sites] == \
+        [(nm, i) for i, nm in enumerate(nttmul.DIAG_SITES + ("COUNT",))]
+    body = re.search(r"typedef struct nttmul_diag_server_state_t \{(.*?)\} nttmul_diag_server_state_t;",
+                     hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = [(t, nm.strip()) for t, names_ in re.findall(r"(u?int32_t) ([\w, ]+);", body)
+              for nm in names_.split(",")]
+    ctype = {"uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32}
+    assert [(nm, ctype[t]) for t, nm in fields] == list(nttmul.DiagServerState._fields_)
 
 
 def test_exports_are_plain_c_abi():

@@ -88,7 +88,7 @@ class Run:
 
     def __init__(self, torch, name, salt):
         self.torch, self.name, self.salt = torch, name, salt
-        self.cp, self.steps = L.SEQUENCES[name]
+        self.cp, self.steps = L.ALL_SEQUENCES[name]
         self.trace = L.model(name)
         self.cus = torch.cuda.get_device_properties(0).multi_processor_count
 
@@ -97,8 +97,9 @@ class Run:
     def prepare(self):
         torch, cp = self.torch, self.cp
         cls = nttmul.MacContext if cp.lib == "mac" else nttmul.Context
+        lib = {"_lib": nttmul.load_diag_library()} if cp.lib == "diag" else {}
         self.ctx = cls(cp.n, cp.q, scratch_mb=cp.scratch_mb, validate=cp.validate, ndev=cp.ndev,
-                       share_devices=cp.share_devices)
+                       share_devices=cp.share_devices, **lib)
         self.P = O.Plan(cp.n, cp.q)
         self.streams = {"A": torch.cuda.Stream(), "B": torch.cuda.Stream()}
         self.io, p0 = [], self.salt

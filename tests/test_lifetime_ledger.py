@@ -8,15 +8,16 @@ model, without a GPU.
   points outside its sequence.
 * The launches of the sequences are rows of dispatch_cases.all_cases(), so the kernel ledger keeps
   describing everything the suite launches.
-* The host-path choice of the model at the boundary batches of sequence A."""
-import os
+* The host-path choice of the model at the boundary batches of sequence A.
+* The resident server's failure and retry paths (SERVER_SEQUENCES): the cool-down and the cap are
+  read from the source, every failure path has its row, and the two paths no sequence can stage
+  are EXEMPT rows with their reasons."""
 import re
 
 import dispatch_cases as D
 import lifetime_cases as L
 
-SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                      "ntt-based-polynomial-multiplier-fpga_amd", "csrc", "nttmul.cpp")
+SOURCE = L.SOURCE
 
 
 def _function(lines, opening):
@@ -35,24 +36,27 @@ def test_every_transition_matches_one_line_of_its_function():
     lines = open(SOURCE).read().split("\n")
     names = [t.name for t in L.TRANSITIONS]
     assert len(names) == len(set(names))
-    for t in L.TRANSITIONS:
+    for t in L.TRANSITIONS + L.EXEMPT:
         hits = [ln for ln in _function(lines, t.func) if re.search(t.line, ln)]
         assert len(hits) == 1, (t.name, t.func, hits)
 
 
 def test_every_transition_is_driven_and_every_claim_confirmed():
     driven = {}
-    for name in L.SEQUENCES:
-        for i, w in enumerate(L.model(name)):
-            for tag in w.tags:
-                driven.setdefault(tag, []).append((name, i))
+    for name in L.ALL_SEQUENCES:
+        for in_vram in (True, False):
+            for i, w in enumerate(L.model(name, in_vram)):
+                for tag in w.tags:
+                    driven.setdefault(tag, []).append((name, i))
     table = {t.name for t in L.TRANSITIONS}
     assert sorted(set(driven) - table) == [], "the model names transitions the table lacks"
+    for t in L.EXEMPT:                      # a reason instead of a step, and no step after all
+        assert t.name not in table and t.name not in driven and len(t.pairs) > 20, t.name
     for t in L.TRANSITIONS:
         assert driven.get(t.name), f"no step of any sequence drives {t.name}"
         assert t.pairs, t.name
         for name, i in t.pairs:
-            cp, steps = L.SEQUENCES[name]
+            cp, steps = L.ALL_SEQUENCES[name]
             assert 0 <= i < len(steps), (t.name, name, i)
             assert L.drives(t.name, cp, L.state_before(name, i), steps[i]), (t.name, name, i)
 
@@ -158,3 +162,72 @@ def test_host_path_choice_at_the_boundaries():
     # two slices: the first chunk is sized by batch / ndev
     g = L.SEQUENCES["G"][0]
     assert [L.host_path(g, L.Step("multiply", "host", 32, b)) for b in (1, 16, 17, 18)] == [2, 2, 2, 0]
+
+
+def test_the_server_failure_sequences_hold_what_the_plan_asks_for():
+    """SERVER_SEQUENCES against the constants of nttmul.cpp: how long the cool-down lasts, when
+    the server is tried again, where the cap falls, and that no step leaves a request posted."""
+    src = open(SOURCE).read()
+    R, M = L.RETRY_CALLS, L.MAX_FAILURES
+    assert f"kServerRetryCalls = {R}, kServerMaxFailures = {M};" in src and R > 8 and M == 3
+    for name, (cp, steps) in L.SERVER_SEQUENCES.items():
+        assert cp.lib == "diag" and cp.ndev == 1
+        assert all(s.place == "host" and 1 <= s.batch <= 4 for s in steps), name
+        for in_vram in (True, False):
+            for w in L.model(name, in_vram):
+                S = w.state["server"]
+                assert S["go_is_served"] and S["failures"] <= M, name
+                assert S["disabled"] == (w.state["server"]["reason"] is not None
+                                         and not S["reason"][2]), name
+    srv = lambda name, i, v=True: L.model(name, v)[i].state["server"]     # noqa: E731
+    # S1: both stalled calls are served by the relaunch inside the spin loop
+    s1 = L.model("S1")
+    assert [w.path for w in s1] == [3] * 5 and srv("S1", 4)["failures"] == 0
+    assert [w.state["server"]["spin"] for w in s1] == [0, 1, 1, 2, 2]
+    assert [w.state["server"]["launches"] for w in s1] == [1, 2, 2, 3, 3]
+    assert L.SEQUENCES is not L.ALL_SEQUENCES and "S1" not in L.SEQUENCES
+    # S2: refused in the middle of a request with the larger request's words behind it, R eligible
+    # calls on the launch path, the range failure and the pointwise call not among them
+    for name, n in (("S2", 256), ("S2_512", 512), ("S2_1024", 1024)):
+        cp, steps = L.SERVER_SEQUENCES[name]
+        m = L.model(name)
+        assert cp.n == n and cp.validate and steps[0].batch == (4 if n == 256 else 1)
+        assert steps[2].batch <= steps[0].batch and len(steps[2].arm) == 2
+        assert m[0].path == 3 and m[2].path in (0, 1, 2) and m[2].state["server"]["failures"] == 1
+        assert m[2].state["server"]["reason"] == (1, "ENOMEM", True, "LAUNCH")
+        cool = m[3:3 + R + 2]
+        assert [s.status for s in steps[3:3 + R + 2]].count("ERANGE") == 1
+        assert [s.entry for s in steps[3:3 + R + 2]].count("pointwise") == 1
+        assert all(w.path != 3 for w in cool) and cool[-1].state["server"]["cooldown"] == 0
+        assert sum("server.cooldown" in w.tags for w in cool) == R
+        retry = m[3 + R + 2]
+        assert retry.path == 3 and steps[3 + R + 2].batch == 1 and "server.relaunch" in retry.tags
+        assert retry.state["server"]["failures"] == 1 and len(m) == R + 7
+    # S3: three failures, each after its cool-down; ten calls on the launch path after the third
+    cp, steps = L.SERVER_SEQUENCES["S3"]
+    armed = [i for i, s in enumerate(steps) if s.arm]
+    assert armed == [0, R + 1, 2 * R + 2] and len(steps) == armed[-1] + 1 + 10
+    assert [srv("S3", i)["reason"] for i in armed] == \
+        [(k, "ENOMEM", k < M, "LAUNCH") for k in (1, 2, 3)]
+    assert all(w.path == 2 for w in L.model("S3")) and srv("S3", len(steps) - 1)["failures"] == M
+    assert not srv("S3", armed[1])["disabled"] and srv("S3", armed[2])["disabled"]
+    # S4: any other error is permanent at once
+    assert srv("S4", 0)["reason"] == (1, "EHIP", False, "LAUNCH") and srv("S4", 0)["disabled"]
+    assert all(w.path == 2 for w in L.model("S4"))
+    # S5: every allocation site, the retry after the cool-down served; the request half's sites
+    # are passed only where the request half is not in device memory
+    for site in L.ALLOC_SITES:
+        name = "S5_" + site.lower()
+        for in_vram in (True, False):
+            reached = not (in_vram and site.startswith("REQ"))
+            m = L.model(name, in_vram)
+            assert (m[0].path == 3) == (not reached), (site, in_vram)
+            assert m[0].state["server"]["failures"] == int(reached)
+            assert m[0].state["server"]["allocated"] == (not reached)
+            assert ("server.alloc_rollback" in m[0].tags) == reached
+            assert [w.path for w in m[R + 1:]] == [3, 3] and m[-1].state["server"]["allocated"]
+            assert m[-1].state["server"]["failures"] == int(reached)
+    # S6: destroyed in cool-down, and permanently switched
+    assert 0 < srv("S6_cool", 5)["cooldown"] < R and not srv("S6_cool", 5)["disabled"]
+    assert srv("S6_off", 3)["disabled"] and not srv("S6_off", 3)["allocated"]
+    assert [w.path for w in L.model("S6_fresh")] == [3, 3]
