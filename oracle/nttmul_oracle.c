@@ -812,6 +812,40 @@ double orc_product_batch(const orc_plan *P, int gs, uint64_t *c, const uint64_t 
   return (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) * 1e-9;
 }
 
+/* One restated transform loop over a batch, in place, OpenMP over the batch: loop `fn` (the order
+ * of oracle.py TRANSFORMS) with plan table `table` on each of `count` polynomials, then, when
+ * scale != 0, every word times scale (the n^-1 of a scaled inverse).  Returns 0, or -1 for an
+ * unknown loop or table. */
+int orc_transform_batch(const orc_plan *P, int fn, int table, uint64_t scale, uint64_t *a,
+                        uint64_t count, int threads) {
+  typedef void (*loop_fn)(uint64_t *, uint32_t, const uint64_t *, uint64_t);
+  static const loop_fn loops[] = {
+      orc_ntt_ct_rev2std, orc_mulntt_ct_rev2std, orc_ntt_ct_std2rev, orc_mulntt_ct_std2rev,
+      orc_ntt_gs_rev2std, orc_nttmul_gs_rev2std, orc_ntt_gs_std2rev, orc_nttmul_gs_std2rev};
+  if (fn < 0 || fn >= (int)(sizeof(loops) / sizeof(loops[0]))) return -1;
+  const uint64_t *tab = orc_plan_table(P, table);
+  if (!tab) return -1;
+  const uint32_t n = P->n;
+  const uint64_t q = P->q;
+#ifdef _OPENMP
+  if (threads <= 0) threads = omp_get_max_threads();
+#else
+  threads = 1;
+#endif
+#pragma omp parallel for schedule(static) num_threads(threads)
+  for (int64_t p = 0; p < (int64_t)count; p++) {
+    loops[fn](a + p * n, n, tab, q);
+    if (scale) orc_scalar_mul_array(a + p * n, n, scale, q);
+  }
+  return 0;
+}
+
+/* c[i] = a[i] * b[i] mod q over `words` words (ntt.C:131 mul_array over a batch), OpenMP. */
+void orc_mul_batch(uint64_t *c, const uint64_t *a, const uint64_t *b, uint64_t words, uint64_t q) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < (int64_t)words; i++) c[i] = mulmod(a[i], b[i], q);
+}
+
 /* C1 (BASELINE.json configs[0]): ONE product on ONE core, timed the way time_testing256.c:147-187
  * times ntt256_product4 -- reps iterations, the inputs restored before each (untimed, :110-116),
  * CLOCK_MONOTONIC around the product call only (:178-181), the average returned in seconds.

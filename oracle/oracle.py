@@ -26,6 +26,12 @@ TABLES = [
     "mixed_powers", "mixed_powers_rev", "inv_mixed_powers", "inv_mixed_powers_rev",
 ]
 
+# the transform loops orc_transform_batch runs, in the order of its table in nttmul_oracle.c
+TRANSFORMS = [
+    "ntt_ct_rev2std", "mulntt_ct_rev2std", "ntt_ct_std2rev", "mulntt_ct_std2rev",
+    "ntt_gs_rev2std", "nttmul_gs_rev2std", "ntt_gs_std2rev", "nttmul_gs_std2rev",
+]
+
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -79,6 +85,10 @@ def _load() -> ctypes.CDLL:
     lib.orc_product_batch.restype = ctypes.c_double
     lib.orc_product_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, _u64p, _u64p, _u64p,
                                       ctypes.c_uint64, ctypes.c_int]
+    lib.orc_transform_batch.restype = ctypes.c_int
+    lib.orc_transform_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_uint64, _u64p, ctypes.c_uint64, ctypes.c_int]
+    lib.orc_mul_batch.argtypes = [_u64p, _u64p, _u64p, ctypes.c_uint64, ctypes.c_uint64]
     lib.orc_num_threads.restype = ctypes.c_int
     lib.orc_time_single.restype = ctypes.c_double
     lib.orc_time_single.argtypes = [ctypes.c_void_p, ctypes.c_int, _u64p, _u64p, _u64p,
@@ -177,6 +187,28 @@ class Plan:
         t = self.table(table)
         getattr(self._lib, "orc_" + name)(_p64(a), self.n, _p64(t), self.q)
         return a
+
+    def transform_batch(self, name: str, a, table: str, scale: int = 0,
+                        threads: int = 0) -> np.ndarray:
+        """transform(name, ., table) on every row of a [count, n] (OpenMP over the rows), each
+        word then times `scale` mod q when scale != 0; returns a new uint64 array."""
+        a = np.array(a, dtype=np.uint64, copy=True)
+        if a.ndim != 2 or a.shape[1] != self.n:
+            raise ValueError("a must have shape [count, n]")
+        if self._lib.orc_transform_batch(self._p, TRANSFORMS.index(name), TABLES.index(table),
+                                         scale, _p64(a), a.shape[0], threads) != 0:
+            raise ValueError(f"oracle: no batch form of {name} on {table}")
+        return a
+
+    def mul_batch(self, a, b) -> np.ndarray:
+        """a[i] * b[i] mod q over arrays of one shape (ntt.C:131 mul_array), OpenMP."""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        if a.shape != b.shape:
+            raise ValueError("a and b must have the same shape")
+        c = np.empty_like(a)
+        self._lib.orc_mul_batch(_p64(c), _p64(a), _p64(b), a.size, self.q)
+        return c
 
     def eval_check(self, c, a, b, points: int = 8) -> int:
         c = np.ascontiguousarray(c, dtype=np.uint64)

@@ -58,6 +58,9 @@ def all_cases():
         out += [Case("moddown", bits, N, BATCH, L, 3) for L in EXACT_L]
     out += [Case(op, 32, N, BATCH, 2, 1) for op in OPS] + [Case(op, 32, N, BATCH, 1, 2) for op in OPS]
     out += [f.case for f in footprint_cases()]
+    # the launches that fill the GPU twice over (tests/test_gpu_scale.py, tests/scale_cases.py)
+    import scale_cases
+    out += scale_cases.cases_of("bconv")
     return out
 
 

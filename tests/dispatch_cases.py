@@ -420,6 +420,24 @@ def units_per_block(case, cus=MI355X_CUS):
     return out
 
 
+DEFAULT_SCRATCH_MB = 512
+
+
+def chunks(case, scratch_mb=0):
+    """csrc/nttmul.cpp run_device / sub_batch: the sub-batches of a device call.  A multi-pass
+    product or transform and a reordered transform go through the scratch, at most scratch_mb MiB
+    per buffer in whole polynomials (of the native word for a multi-pass call, of the caller's
+    word for a reordered fused transform), never less than one; every other call is one launch
+    over the whole batch."""
+    multipass = case.n > 4096 and case.op in ("multiply", "transform")
+    reorder = case.op == "transform" and bool(case.mode & 1) != bool(case.mode & 2)
+    if not (multipass or reorder) or not case.batch:
+        return [case.batch]
+    poly = case.n * ((native_bits(case.q) if multipass else case.word_bits) // 8)
+    chunk = max(1, min(case.batch, ((scratch_mb or DEFAULT_SCRATCH_MB) << 20) // poly))
+    return [min(chunk, case.batch - p) for p in range(0, case.batch, chunk)]
+
+
 # Kernels whose launches never end in a partial workgroup, whatever the batch: (regular expression
 # over the kernel_key, reason).  Every other multi-unit kernel needs a footprint case with one.
 FP_ALWAYS_WHOLE = (
@@ -521,6 +539,9 @@ def new_cases():
     # the launches of the call sequences over long-lived contexts (tests/test_gpu_lifetime.py)
     from lifetime_cases import lifetime_cases
     out += lifetime_cases()
+    # the launches that fill the GPU twice over (tests/test_gpu_scale.py, tests/scale_cases.py)
+    import scale_cases
+    out += scale_cases.cases_of("plain")
     return out
 
 

@@ -111,6 +111,9 @@ def all_cases():
     out += [Case(op, n, m, 3, many_ks(n, 3) if op == "ntt_many" else (5,)) for op in OPS]
     out += [Case(op, n, m, HOST_BATCH, (ref.element(n, 1),)) for n, m in HOST for op in OPS[:2]]
     out += [f.case for f in footprint_cases()]
+    # the launches that fill the GPU twice over (tests/test_gpu_scale.py, tests/scale_cases.py)
+    import scale_cases
+    out += scale_cases.cases_of("galois")
     return out
 
 

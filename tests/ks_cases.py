@@ -112,6 +112,9 @@ def all_cases():
     out += [Case(op, bits, n, CHAIN_BATCH, *CHAIN_SHAPE) for op in OPS for bits in (32, 64)
             for n, _ in CHAIN]
     out += [f.case for f in footprint_cases()]
+    # the launches that fill the GPU twice over (tests/test_gpu_scale.py, tests/scale_cases.py)
+    import scale_cases
+    out += scale_cases.cases_of("ks")
     return out
 
 

@@ -66,6 +66,9 @@ def all_cases():
     n, batch, terms = HOST
     out += [Case(n, q, w, terms, False, batch) for q in moduli_at(n) for w in D.word_options(q)]
     out += [f.case for f in footprint_cases()]
+    # the launches that fill the GPU twice over (tests/test_gpu_scale.py, tests/scale_cases.py)
+    import scale_cases
+    out += scale_cases.cases_of("mac")
     return out
 
 

@@ -108,6 +108,9 @@ def all_cases():
             q, p = ks_ref.bases(bits, L, P)
             out.append(Case(n, q + p, CHAIN_BATCH, -(-L // alpha), 2, True))
     out += [f.case for f in footprint_cases()]
+    # the launches that fill the GPU twice over (tests/test_gpu_scale.py, tests/scale_cases.py)
+    import scale_cases
+    out += scale_cases.cases_of("macn")
     return out
 
 

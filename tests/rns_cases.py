@@ -78,6 +78,9 @@ def all_cases():
     out += [Case(op, n, m, HOST_BATCH, HOST_TERMS if op == "mac" else 1, s)
             for n, m in HOST for op, s in [(o, False) for o in OPS] + [("mac", True)]]
     out += [f.case for f in footprint_cases()]
+    # the launches that fill the GPU twice over (tests/test_gpu_scale.py, tests/scale_cases.py)
+    import scale_cases
+    out += scale_cases.cases_of("rns")
     return out
 
 

@@ -102,6 +102,9 @@ def all_cases():
             for n, m in HOST for op, s in [(o, False) for o in OPS] + [("mac", True)]]
     out += subbatch_cases()
     out += [f.case for f in footprint_cases()]
+    # the launches that fill the GPU twice over (tests/test_gpu_scale.py, tests/scale_cases.py)
+    import scale_cases
+    out += scale_cases.cases_of("rnsmp")
     return out
 
 

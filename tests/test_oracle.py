@@ -139,6 +139,36 @@ def test_wrappers_golden(golden_dir):
             assert np.array_equal(got, exp.astype(np.uint64)), name
 
 
+def test_transform_batch_is_the_single_transform_row_by_row():
+    """Plan.transform_batch (OpenMP over the rows) equals Plan.transform on every row, for every
+    loop it offers with every table the wrappers pair it with, on one and on several threads, with
+    and without the scaling of an inverse; Plan.mul_batch equals Python integers."""
+    rng = np.random.default_rng(11)
+    pairs = sorted(set(WRAPPERS.values()))
+    assert {fn for fn, _ in pairs} == set(O.TRANSFORMS)
+    for n, q in ((256, Q0), (1024, 2013265921), (512, 0x3FFFFFFFFFE80001)):
+        P = O.Plan(n, q)
+        x = rng.integers(0, q, (7, n), dtype=np.uint64)
+        x[0, :], x[6, :] = q - 1, 0
+        keep = x.copy()
+        for fn, tab in pairs:
+            for scale in (0, P.inv_n):
+                want = np.stack([P.transform(fn, row, tab) for row in x])
+                if scale:
+                    want = np.array([[int(v) * scale % q for v in row] for row in want],
+                                    dtype=np.uint64)
+                for threads in (1, 3):
+                    got = P.transform_batch(fn, x, tab, scale, threads)
+                    assert np.array_equal(got, want), (n, q, fn, tab, scale, threads)
+        assert np.array_equal(x, keep)
+        y = rng.integers(0, q, (7, n), dtype=np.uint64)
+        want = np.array([int(a) * int(b) % q for a, b in zip(x.ravel(), y.ravel())],
+                        dtype=np.uint64).reshape(x.shape)
+        assert np.array_equal(P.mul_batch(x, y), want)
+    with pytest.raises(ValueError):
+        P.transform_batch("ntt_ct_std2rev", x[0], "omega_powers_rev")
+
+
 def _bitrev_perm(v):
     b = int(np.log2(len(v)))
     return v[[int(format(i, f"0{b}b")[::-1], 2) for i in range(len(v))]]
