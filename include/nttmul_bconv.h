@@ -51,7 +51,8 @@
  *   - exact conversion, that is the alpha correction (floating-point as Halevi-Polyakov-Shoup, or
  *     a redundant modulus);
  *   - rounding instead of flooring in moddown;
- *   - NTT-domain inputs, or a fused inverse transform -> convert -> forward transform pipeline;
+ *   - NTT-domain inputs, or a fused inverse transform -> convert -> forward transform pipeline
+ *     (for ModDown that is nttmul_mdntt.h, lib/libnttmul_mdntt.so);
  *   - n > 4096, the class 2^31 <= q < 2^32, and 64-bit storage of 32-bit limbs;
  *   - a chunked or multi-device host path (the host forms below are deliberately simple);
  *   - a bench.py mode (tools/bench_bconv.py measures these calls).

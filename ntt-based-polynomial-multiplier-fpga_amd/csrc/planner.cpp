@@ -79,7 +79,7 @@ static uint64_t companion(uint64_t w, uint64_t q, int bits) {
 // -q^-1 mod 2^32)
 // sgn (Arith32P only): the pair for a signed multiplicand x in [-2^31, 2^31) — the high word
 // absorbs the sign of the low one (v_mul_hi_i32 reads it as int32): c + (v >> 31)
-static void tw_pair(uint64_t w, uint64_t q, int bits, uint64_t *v, uint64_t *c, bool sgn = false) {
+void tw_pair(uint64_t w, uint64_t q, int bits, uint64_t *v, uint64_t *c, bool sgn) {
   if (bits == 32 && a32_kind(q) == A32Kind::Plantard) {
     uint64_t inv = q;  // q^-1 mod 2^64 (Newton on the 2-adic inverse)
     for (int i = 0; i < 6; i++) inv *= 2 - q * inv;

@@ -42,4 +42,10 @@ struct Plan {
 // Returns 0 or a negative NTTMUL_E* status.
 int make_plan(uint32_t n, uint64_t q, uint64_t psi, Plan *out, bool cyclic = false);
 
+// The (value, companion) pair the device multiplies by w with, for words of `bits` under q, as
+// make_plan builds every twiddle and scale constant (sgn: the form for a signed multiplicand, the
+// inverse butterflies' differences on Arith32P).  For a library that folds a factor of its own
+// into a plan's scale (mdntt.cpp).
+void tw_pair(uint64_t w, uint64_t q, int bits, uint64_t *v, uint64_t *c, bool sgn = false);
+
 }  // namespace nttmul

@@ -1708,6 +1708,95 @@ class RnsMpHoistContext(_HoistOps, RnsMpMacnContext):
                          _flags(validate, cyclic, share_devices), scratch_mb)
 
 
+# ---- ModDown and rescale on NTT-domain limbs (include/nttmul_mdntt.h) ----------------------------
+
+MDNTT_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_mdntt.so")
+MDNTT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_mdntt.h")
+
+
+class MdNttInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("q_limbs", ctypes.c_uint32),
+                ("p_limbs", ctypes.c_uint32), ("word_bits", ctypes.c_uint32),
+                ("ndev", ctypes.c_int), ("scratch_mb", ctypes.c_uint32)]
+
+
+def load_mdntt_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_mdntt.so (include/nttmul_mdntt.h): the ABI and kernels of
+    libnttmul_hoist.so plus the NTT-domain ModDown.  The other loaders are unaffected."""
+    return _load_limb_library(MDNTT_LIB_PATH, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn,
+                              _bind_hoist, _bind_mdntt)
+
+
+def _bind_mdntt(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    _bind_handle(lib, "nttmul_mdntt", MdNttInfo, [u64p, u32, u64p, u32])
+    lib.nttmul_mdntt_moddown_device.argtypes = [vp, vp, vp, sz, i32, vp]
+    lib.nttmul_mdntt_moddown.argtypes = [vp, vp, vp, sz]
+    lib.nttmul_mdntt_kernel_name.argtypes = [vp, ctypes.c_char_p, sz]
+
+
+def mdntt_exported_symbols() -> list:
+    """Function names declared in include/nttmul_mdntt.h."""
+    return _header_symbols(MDNTT_HEADER_PATH, "nttmul_mdntt_")
+
+
+class NttModDown(_Handle):
+    """nttmul_mdntt: the bases Q = q (L primes) and P = p (K primes), disjoint and of one word
+    class, for one degree n in 256 .. 65536 (include/nttmul_mdntt.h).  moddown maps x_hat
+    [batch, L + K, n], every limb in NTT order as RnsContext / RnsMpContext.forward writes it, to
+    [batch, L, n] in NTT order: forward over q of KeySwitchBasis.moddown of inverse over q + p of
+    x_hat, bit for bit, with only the K limbs of p transformed back.  p = (the last prime,) is the
+    CKKS / BGV rescale.
+
+    Caller memory: operands need the alignment of their word only; out must not overlap x_hat;
+    a call writes exactly batch * L * n words of out and never writes x_hat.
+
+    close() waits for the last use of the context's scratch, not for the streams passed to
+    moddown_device: synchronise them first."""
+
+    _PREFIX = "nttmul_mdntt"
+    _NAME_CAP = 256
+
+    def __init__(self, n: int, q, p, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False, scratch_mb: int = 0):
+        q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
+        prm.ndev, prm.first_dev, prm.scratch_mb = ndev, first_dev, scratch_mb
+        info = MdNttInfo()
+        self._open(load_mdntt_library(), info, prm, qa, len(q), pa, len(p))
+        self.n, self.word_bits = info.n, info.word_bits
+        self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
+        self.q, self.p = tuple(q), tuple(p)
+        self.first_dev = first_dev
+
+    def kernel_name(self) -> str:
+        """nttmul_mdntt_kernel_name: a sub-batch's kernels joined by " + ", e.g.
+        "k_mdntt_inv<Arith32P,u32,12> + k_mdntt_fwd<Arith32P,u32,12>"."""
+        buf = ctypes.create_string_buffer(self._NAME_CAP)
+        st = self._c.kernel_name(self._h, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def moddown_device(self, out, x_hat, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        x_hat [batch][L + K][n] -> out [batch][L][n]."""
+        dev = self.first_dev if dev is None else dev
+        args = [_dev_arg(t, batch * k, self.n, self.word_bits, dev)
+                for t, k in zip((out, x_hat), (self.q_limbs, self.q_limbs + self.p_limbs))]
+        self._check(self._c.moddown_device(self._h, *args, batch, dev, stream or None))
+
+    def moddown(self, x_hat) -> np.ndarray:
+        """x_hat of shape [batch, L + K, n]; returns [batch, L, n]."""
+        ext = self.q_limbs + self.p_limbs
+        x_hat = np.ascontiguousarray(x_hat, dtype=self.io_dtype)
+        if x_hat.ndim != 3 or x_hat.shape[1:] != (ext, self.n):
+            raise ValueError(f"moddown: x_hat must have shape [batch, {ext}, {self.n}]")
+        out = np.empty((x_hat.shape[0], self.q_limbs, self.n), dtype=self.io_dtype)
+        self._check(self._c.moddown(self._h, out.ctypes.data, x_hat.ctypes.data, x_hat.shape[0]))
+        return out
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
