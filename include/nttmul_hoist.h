@@ -67,7 +67,7 @@
  * Out of scope here:
  *   - a per-batch b_hat;
  *   - more than two components;
- *   - NTT-domain output;
+ *   - NTT-domain output (nttmul_ksntt_mac of nttmul_ksntt.h, lib/libnttmul_ksntt.so);
  *   - the rotation of the c_0 part of a ciphertext (nttmul_galois_coeff does it);
  *   - a fused modup or moddown;
  *   - a bench.py mode (tools/bench_hoist.py measures these calls).

@@ -69,8 +69,9 @@
  *   - one call that runs the whole key switch on scratch of its own;
  *   - a mac that shares the forward transforms between the two key components: that is
  *     nttmul_macn.h (lib/libnttmul_macn.so), whose one call replaces the two mac_ntt calls above;
- *   - NTT-domain input or output, that is a fused inverse -> modup -> forward pipeline (ModDown of
- *     NTT-domain limbs is nttmul_mdntt.h, lib/libnttmul_mdntt.so);
+ *   - NTT-domain input or output, that is a fused inverse -> modup -> forward pipeline (ModUp of
+ *     NTT-domain limbs is nttmul_ksntt.h, lib/libnttmul_ksntt.so; ModDown of NTT-domain limbs is
+ *     nttmul_mdntt.h, lib/libnttmul_mdntt.so);
  *   - exact conversion (the alpha correction), and rounding instead of flooring in moddown;
  *   - raising nttmul_bconv_create's own n limit (it stays at 4096);
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC), the class 2^31 <= q < 2^32;

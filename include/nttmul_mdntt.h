@@ -61,8 +61,9 @@
  * Out of scope here:
  *   - rounding instead of flooring (add floor(P / 2) before the call for it);
  *   - a P part in coefficient order, or a coefficient-order output;
- *   - NTT-domain output of nttmul_*_macn_ntt / nttmul_*_hoist_ntt, which would let the whole key
- *     switch end here at dnum (L + K) + 2K + 2L transforms: the stated follow-up;
+ *   - NTT-domain output of nttmul_*_macn_ntt / nttmul_*_hoist_ntt (nttmul_ksntt.h,
+ *     lib/libnttmul_ksntt.so, has the hoisted mac with NTT-domain output and the ModUp in front of
+ *     it, so that the whole key switch ends here);
  *   - exact conversion (the alpha correction);
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC), the class 2^31 <= q < 2^32;
  *   - a chunked or multi-device host path (the host form below is deliberately simple);

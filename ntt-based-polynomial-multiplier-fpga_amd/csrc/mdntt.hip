@@ -50,18 +50,29 @@ static const TwPair<typename A::word> *p_twiddles(const MdTables &T) {
   return (const TwPair<typename A::word> *)T.tw + (((size_t)T.L * 2) << T.logn);
 }
 
+// The inverse half, n <= 4096: limb L + j of x_hat -> y (scr[kMdY])
+template <class A, class IO>
+static hipError_t single_inv(const MdTables &T, const void *xh, size_t cnt, void *const *scr,
+                             const Emit &E) {
+  using W = typename A::word;
+  return with_logn(T.logn, [&](auto logs) {
+    constexpr int LOGS = decltype(logs)::value, PB = 256 / ((1 << LOGS) / 16);
+    constexpr int PBI = PB * xform_upg<A, 0, 1>();
+    return emit_p_limbs(E, md_name<A, IO>("k_mdntt_inv", LOGS), k_mdntt_inv<A, IO, LOGS>,
+                        (cnt + PBI - 1) / PBI, T.K, (const KParams<A> *)T.tab_inv,
+                        p_twiddles<A>(T), (const IO *)xh, (W *)scr[kMdY], cnt, T.L, T.K);
+  });
+}
+
 // n <= 4096: the class is k_rns_xform's, plain Arith32P at every degree, Arith64 on 64-bit words
 template <class A, class IO>
 static hipError_t single(const MdTables &T, void *out, const void *xh, size_t cnt,
                          void *const *scr, const Emit &E) {
   using W = typename A::word;
+  const hipError_t e = single_inv<A, IO>(T, xh, cnt, scr, E);
+  if (e != hipSuccess) return e;
   return with_logn(T.logn, [&](auto logs) {
     constexpr int LOGS = decltype(logs)::value, PB = 256 / ((1 << LOGS) / 16);
-    constexpr int PBI = PB * xform_upg<A, 0, 1>();
-    hipError_t e = emit_p_limbs(E, md_name<A, IO>("k_mdntt_inv", LOGS), k_mdntt_inv<A, IO, LOGS>,
-                                (cnt + PBI - 1) / PBI, T.K, (const KParams<A> *)T.tab_inv,
-                                p_twiddles<A>(T), (const IO *)xh, (W *)scr[kMdY], cnt, T.L, T.K);
-    if (e != hipSuccess) return e;
     return emit_q_fastest(E, md_name<A, IO>("k_mdntt_fwd", LOGS), k_mdntt_fwd<A, IO, LOGS>,
                           (cnt + PB - 1) / PB, T.L, (const KParams<A> *)T.tab_fwd,
                           (const TwPair<W> *)T.tw, (const BconvTo<W> *)T.to, (const W *)T.w,
@@ -69,10 +80,11 @@ static hipError_t single(const MdTables &T, void *out, const void *xh, size_t cn
   });
 }
 
-// n > 4096: one split per (class, n), 2^L1 x 4096
+// The inverse half, n > 4096: the rows of limb L + j into scr[kMdYLazy], the column pass into y
+// (scr[kMdY])
 template <class A, class IO, int L1>
-static hipError_t passes(const MdTables &T, void *out, const void *xh, size_t cnt,
-                         void *const *scr, const Emit &E) {
+static hipError_t passes_inv(const MdTables &T, const void *xh, size_t cnt, void *const *scr,
+                             const Emit &E) {
   using W = typename A::word;
   hipError_t e = emit_p_limbs(E, md_name<A, IO>("k_mdntt_inv_rows", L1),
                               k_mdntt_inv_rows<A, IO, L1>, cnt << L1, T.K,
@@ -86,7 +98,15 @@ static hipError_t passes(const MdTables &T, void *out, const void *xh, size_t cn
   V.word_bits = T.word_bits;
   V.tab[kRnsTransform] = T.tab_inv;
   V.tw = p_twiddles<A>(T);
-  e = launch_rnsmp_cols(V, 1, scr[kMdY], scr[kMdYLazy], cnt, E.s, E.describe);
+  return launch_rnsmp_cols(V, 1, scr[kMdY], scr[kMdYLazy], cnt, E.s, E.describe);
+}
+
+// n > 4096: one split per (class, n), 2^L1 x 4096
+template <class A, class IO, int L1>
+static hipError_t passes(const MdTables &T, void *out, const void *xh, size_t cnt,
+                         void *const *scr, const Emit &E) {
+  using W = typename A::word;
+  hipError_t e = passes_inv<A, IO, L1>(T, xh, cnt, scr, E);
   if (e != hipSuccess) return e;
   e = emit_q_fastest(E, md_name<A, IO>("k_mdntt_cols_fwd", L1), k_mdntt_cols_fwd<A, IO, L1>,
                      ((cnt << kMpLogs) + 255) / 256, T.L, (const KParams<A> *)T.tab_fwd,
@@ -116,6 +136,26 @@ static hipError_t dispatch_words(const MdTables &T, void *out, const void *xh, s
   if (!T.L || !T.K) return hipErrorInvalidValue;
   return T.word_bits == 32 ? dispatch<Arith32P, uint32_t>(T, out, xh, cnt, scr, E)
                            : dispatch<Arith64, uint64_t>(T, out, xh, cnt, scr, E);
+}
+
+template <class A, class IO>
+static hipError_t dispatch_inv(const MdTables &T, const void *xh, size_t cnt, void *const *scr,
+                               const Emit &E) {
+  switch (T.logn) {
+    case 13: return passes_inv<A, IO, 1>(T, xh, cnt, scr, E);
+    case 14: return passes_inv<A, IO, 2>(T, xh, cnt, scr, E);
+    case 15: return passes_inv<A, IO, 3>(T, xh, cnt, scr, E);
+    case 16: return passes_inv<A, IO, 4>(T, xh, cnt, scr, E);
+    default: return T.logn <= 12 ? single_inv<A, IO>(T, xh, cnt, scr, E) : hipErrorNotSupported;
+  }
+}
+
+hipError_t launch_mdntt_inverse(const MdTables &T, const void *x_hat, size_t cnt,
+                                void *const *scr, hipStream_t s, std::string *describe) {
+  if (!T.K) return hipErrorInvalidValue;
+  const Emit E{s, describe};
+  return T.word_bits == 32 ? dispatch_inv<Arith32P, uint32_t>(T, x_hat, cnt, scr, E)
+                           : dispatch_inv<Arith64, uint64_t>(T, x_hat, cnt, scr, E);
 }
 
 hipError_t launch_mdntt(const MdTables &T, void *out, const void *x_hat, size_t cnt,

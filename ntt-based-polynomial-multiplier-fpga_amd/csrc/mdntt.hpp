@@ -27,6 +27,13 @@ enum MdScratch { kMdY = 0, kMdYLazy = 1, kMdT = 2, kMdScratch = 3 };
 // The launches of one sub-batch on stream s: x_hat [cnt][L + K][n] -> out [cnt][L][n]
 hipError_t launch_mdntt(const MdTables &T, void *out, const void *x_hat, size_t cnt,
                         void *const *scr, hipStream_t s);
+// The inverse half of launch_mdntt alone: the limbs L .. L + K - 1 of x_hat [cnt][L + K][n] -> y
+// [cnt][K][n] in scr[kMdY], coefficient order, canonical, scaled by what tab_inv folds
+// (k_mdntt_inv, or k_mdntt_inv_rows through scr[kMdYLazy] and k_rnsmp_cols_inv).  L = 0 reads a
+// compact [cnt][K][n] operand: what the ModUp of include/nttmul_ksntt.h inverts (ksntt.cpp).
+// With `describe` set nothing is launched and the kernels' names are appended to it.
+hipError_t launch_mdntt_inverse(const MdTables &T, const void *x_hat, size_t cnt,
+                                void *const *scr, hipStream_t s, std::string *describe);
 // The kernels launch_mdntt launches for T, joined by " + ": the dry run of the launching
 // statements themselves (kernels_dev.hpp Emit)
 hipError_t describe_mdntt(const MdTables &T, std::string *out);

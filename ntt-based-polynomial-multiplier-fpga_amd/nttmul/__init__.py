@@ -1797,6 +1797,141 @@ class NttModDown(_Handle):
         return out
 
 
+# ---- ModUp and the key mac on NTT-domain limbs (include/nttmul_ksntt.h) --------------------------
+
+KSNTT_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_ksntt.so")
+KSNTT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_ksntt.h")
+KSNTT_OPS = ("modup", "mac")
+
+
+class KsNttInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("q_limbs", ctypes.c_uint32),
+                ("p_limbs", ctypes.c_uint32), ("digit_limbs", ctypes.c_uint32),
+                ("digits", ctypes.c_uint32), ("word_bits", ctypes.c_uint32),
+                ("ndev", ctypes.c_int), ("scratch_mb", ctypes.c_uint32)]
+
+
+def load_ksntt_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_ksntt.so (include/nttmul_ksntt.h): the ABI and kernels of
+    libnttmul_mdntt.so plus the NTT-domain ModUp and key mac.  The other loaders are unaffected."""
+    return _load_limb_library(KSNTT_LIB_PATH, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn,
+                              _bind_hoist, _bind_mdntt, _bind_ksntt)
+
+
+def _bind_ksntt(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u64p, u32p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+    _bind_handle(lib, "nttmul_ksntt", KsNttInfo, [u64p, u32, u64p, u32, u32])
+    lib.nttmul_ksntt_modup_device.argtypes = [vp, vp, vp, sz, i32, vp]
+    lib.nttmul_ksntt_modup.argtypes = [vp, vp, vp, sz]
+    lib.nttmul_ksntt_mac_device.argtypes = [vp, vp, vp, vp, u32p, u32, sz, u32, u32, i32, vp]
+    lib.nttmul_ksntt_mac.argtypes = [vp, vp, vp, vp, u32p, u32, sz, u32, u32]
+    lib.nttmul_ksntt_kernel_name.argtypes = [vp, i32, u32, ctypes.c_char_p, sz]
+
+
+def ksntt_exported_symbols() -> list:
+    """Function names declared in include/nttmul_ksntt.h."""
+    return _header_symbols(KSNTT_HEADER_PATH, "nttmul_ksntt_")
+
+
+class NttKeySwitch(_Handle):
+    """nttmul_ksntt: the bases Q = q (L primes) and P = p (K primes), disjoint and of one word
+    class, with digits of alpha limbs of Q, for one degree n in 256 .. 65536
+    (include/nttmul_ksntt.h).  Every limb of every operand is in NTT order, as RnsContext /
+    RnsMpContext.forward writes it.
+
+    modup maps x_hat [batch, L, n] to [batch, digits, L + K, n]: forward over q + p of
+    KeySwitchBasis.modup of inverse over q of x_hat, bit for bit, with a digit's own limbs copied.
+    mac is the hoisted mac with NTT-domain output,
+    c_hat[p][r][i] = sum_t sigma_{k_r}(a_hat[p][t]) o b_hat[r][i][t], forward of hoist_ntt bit for
+    bit; its c_hat is what NttModDown.moddown reads.
+
+    Caller memory: operands need the alignment of their word only; the output must overlap no
+    input; modup writes exactly batch * digits * (L + K) * n words and mac
+    batch * rots * comps * (L + K) * n, and neither writes an input.
+
+    close() waits for the last use of the context's scratch, not for the streams passed to the
+    *_device calls: synchronise them first."""
+
+    _PREFIX = "nttmul_ksntt"
+    _NAME_CAP = 256
+
+    def __init__(self, n: int, q, p, alpha: int, ndev: int = 1, first_dev: int = 0,
+                 validate: bool = False, cyclic: bool = False, share_devices: bool = False,
+                 scratch_mb: int = 0):
+        q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
+        prm.ndev, prm.first_dev, prm.scratch_mb = ndev, first_dev, scratch_mb
+        info = KsNttInfo()
+        self._open(load_ksntt_library(), info, prm, qa, len(q), pa, len(p), alpha)  # self.info
+        self.n, self.word_bits = info.n, info.word_bits
+        self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
+        self.limbs = info.q_limbs + info.p_limbs
+        self.digit_limbs, self.digits = info.digit_limbs, info.digits
+        self.scratch_mb = info.scratch_mb
+        self.q, self.p = tuple(q), tuple(p)
+        self.first_dev = first_dev
+
+    def kernel_name(self, op, comps: int = 1) -> str:
+        """nttmul_ksntt_kernel_name for op 0..1 or "modup" / "mac": a sub-batch's kernels joined
+        by " + ", e.g. "k_mdntt_inv<Arith32P,u32,12> + k_ksntt_fwd<Arith32P,u32,12>" or
+        "k_ksntt_mac<Arith64,u64,2>"."""
+        op = KSNTT_OPS.index(op) if isinstance(op, str) else int(op)
+        buf = ctypes.create_string_buffer(self._NAME_CAP)
+        st = self._c.kernel_name(self._h, op, comps, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def modup_device(self, up_hat, x_hat, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        x_hat [batch][L][n] -> up_hat [batch][digits][L + K][n]."""
+        dev = self.first_dev if dev is None else dev
+        args = [_dev_arg(t, batch * k, self.n, self.word_bits, dev)
+                for t, k in zip((up_hat, x_hat), (self.digits * self.limbs, self.q_limbs))]
+        self._check(self._c.modup_device(self._h, *args, batch, dev, stream or None))
+
+    def modup(self, x_hat) -> np.ndarray:
+        """x_hat of shape [batch, L, n]; returns [batch, digits, L + K, n]."""
+        x_hat = np.ascontiguousarray(x_hat, dtype=self.io_dtype)
+        if x_hat.ndim != 3 or x_hat.shape[1:] != (self.q_limbs, self.n):
+            raise ValueError(f"modup: x_hat must have shape [batch, {self.q_limbs}, {self.n}]")
+        out = np.empty((x_hat.shape[0], self.digits, self.limbs, self.n), dtype=self.io_dtype)
+        self._check(self._c.modup(self._h, out.ctypes.data, x_hat.ctypes.data, x_hat.shape[0]))
+        return out
+
+    def mac_device(self, c_hat, a_hat, b_hat, ks, batch: int, terms: int, comps: int,
+                   dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        a_hat [batch][terms][L + K][n], b_hat [len(ks)][comps][terms][L + K][n],
+        c_hat [batch][len(ks)][comps][L + K][n]; ks: the rotations, host integers."""
+        dev = self.first_dev if dev is None else dev
+        ks = [int(k) for k in ks]
+        rots = len(ks)
+        polys = (batch * rots * comps, batch * terms, rots * comps * terms)
+        args = [_dev_arg(t, k * self.limbs, self.n, self.word_bits, dev)
+                for t, k in zip((c_hat, a_hat, b_hat), polys)]
+        karr = (ctypes.c_uint32 * max(1, rots))(*ks)
+        self._check(self._c.mac_device(self._h, *args, karr, rots, batch, terms, comps, dev,
+                                       stream or None))
+
+    def mac(self, a_hat, b_hat, ks) -> np.ndarray:
+        """a_hat of shape [batch, terms, L + K, n]; b_hat of shape [rots, comps, terms, L + K, n]
+        with rots = len(ks).  Returns c_hat of shape [batch, rots, comps, L + K, n]."""
+        a_hat = np.ascontiguousarray(a_hat, dtype=self.io_dtype)
+        b_hat = np.ascontiguousarray(b_hat, dtype=self.io_dtype)
+        ks = [int(k) for k in ks]
+        if a_hat.ndim != 4 or a_hat.shape[2:] != (self.limbs, self.n) or a_hat.shape[1] == 0:
+            raise ValueError(f"mac: a_hat must have shape [batch, terms > 0, {self.limbs}, {self.n}]")
+        if b_hat.ndim != 5 or b_hat.shape[-3:] != a_hat.shape[1:] or b_hat.shape[0] != len(ks):
+            raise ValueError("mac: b_hat must have shape [len(ks), comps, terms, L + K, n]")
+        rots, comps = b_hat.shape[:2]
+        c = np.empty((a_hat.shape[0], rots, comps, self.limbs, self.n), dtype=self.io_dtype)
+        karr = (ctypes.c_uint32 * max(1, rots))(*ks)
+        self._check(self._c.mac(self._h, c.ctypes.data, a_hat.ctypes.data, b_hat.ctypes.data, karr,
+                                rots, a_hat.shape[0], a_hat.shape[1], comps))
+        return c
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
