@@ -79,7 +79,8 @@
  * Out of scope here:
  *   - rounding in ModDown, and exact conversion (the alpha correction);
  *   - a b_hat per batch entry, or more than NTTMUL_MACN_MAX_COMPS components;
- *   - summing the rotations before ModDown (rotate-and-sum in Q u P);
+ *   - summing the rotations before ModDown (rotate-and-sum in Q u P): nttmul_lintrans.h's
+ *     nttmul_lintrans_apply, in lib/libnttmul_lintrans.so;
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC), the class 2^31 <= q < 2^32;
  *   - a chunked or multi-device host path (the host forms below are deliberately simple);
  *   - a bench.py mode (tools/bench_ksntt.py measures these calls).

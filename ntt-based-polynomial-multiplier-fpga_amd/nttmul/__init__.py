@@ -1932,6 +1932,129 @@ class NttKeySwitch(_Handle):
         return c
 
 
+# ---- the weighted sum of rotations before ModDown (include/nttmul_lintrans.h) --------------------
+
+LINTRANS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_lintrans.so")
+LINTRANS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_lintrans.h")
+
+
+class LinTransInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("q_limbs", ctypes.c_uint32),
+                ("p_limbs", ctypes.c_uint32), ("word_bits", ctypes.c_uint32),
+                ("ndev", ctypes.c_int)]
+
+
+def load_lintrans_library(path: str = LINTRANS_LIB_PATH) -> ctypes.CDLL:
+    """Load lib/libnttmul_lintrans.so (include/nttmul_lintrans.h): the ABI and kernels of
+    libnttmul_ksntt.so plus the weighted sum of rotations.  The other loaders are unaffected."""
+    return _load_limb_library(path, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn, _bind_hoist,
+                              _bind_mdntt, _bind_ksntt, _bind_lintrans)
+
+
+def _bind_lintrans(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u64p, u32p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+    _bind_handle(lib, "nttmul_lintrans", LinTransInfo, [u64p, u32, u64p, u32])
+    lib.nttmul_lintrans_apply_device.argtypes = [vp, vp, vp, vp, vp, vp, u32p, u32, sz, u32, u32,
+                                                 i32, vp]
+    lib.nttmul_lintrans_apply.argtypes = [vp, vp, vp, vp, vp, vp, u32p, u32, sz, u32, u32]
+    lib.nttmul_lintrans_kernel_name.argtypes = [vp, u32, i32, ctypes.c_char_p, sz]
+
+
+def lintrans_exported_symbols() -> list:
+    """Function names declared in include/nttmul_lintrans.h."""
+    return _header_symbols(LINTRANS_HEADER_PATH, "nttmul_lintrans_")
+
+
+class NttLinTrans(_Handle):
+    """nttmul_lintrans: the bases Q = q (L primes) and P = p (K primes), disjoint and of one word
+    class, for one degree n in 256 .. 65536 (include/nttmul_lintrans.h).  Every limb of every
+    operand is in NTT order, as RnsContext / RnsMpContext.forward writes it.
+
+    apply is the weighted sum of rotations in Q u P,
+    c_hat[p][i] = sum_r w_hat[r] o (sum_t sigma_{k_r}(a_hat[p][t]) o b_hat[r][i][t]
+                                    + [i = 0] P sigma_{k_r}(c0_hat[p])),
+    one launch for any number of rotations.  w_hat = None: every weight is 1.  c0_hat = None: that
+    term is dropped.  Its c_hat is what NttModDown.moddown reads with batch * comps polynomials.
+
+    Caller memory: operands need the alignment of their word only; the output must overlap no
+    input; apply writes exactly batch * comps * (L + K) * n words and never writes an input."""
+
+    _PREFIX = "nttmul_lintrans"
+    _NAME_CAP = 256
+
+    def __init__(self, n: int, q, p, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False, lib_path: Optional[str] = None):
+        q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
+        prm.ndev, prm.first_dev = ndev, first_dev
+        info = LinTransInfo()
+        lib = load_lintrans_library(lib_path) if lib_path else load_lintrans_library()
+        self._open(lib, info, prm, qa, len(q), pa, len(p))  # self.info
+        self.n, self.word_bits = info.n, info.word_bits
+        self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
+        self.limbs = info.q_limbs + info.p_limbs
+        self.q, self.p = tuple(q), tuple(p)
+        self.first_dev = first_dev
+
+    def kernel_name(self, comps: int = 1, weighted: bool = False) -> str:
+        """nttmul_lintrans_kernel_name, e.g. "k_lintrans<Arith64,u64,2,1>"."""
+        buf = ctypes.create_string_buffer(self._NAME_CAP)
+        st = self._c.kernel_name(self._h, comps, int(bool(weighted)), buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def apply_device(self, c_hat, a_hat, b_hat, k, batch: int, terms: int, comps: int,
+                     w_hat=None, c0_hat=None, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        a_hat [batch][terms][L + K][n], b_hat [len(k)][comps][terms][L + K][n],
+        w_hat [len(k)][L + K][n] or None, c0_hat [batch][L][n] or None,
+        c_hat [batch][comps][L + K][n]; k: the rotations, host integers."""
+        dev = self.first_dev if dev is None else dev
+        k = [int(x) for x in k]
+        rots = len(k)
+        polys = (batch * comps, batch * terms, rots * comps * terms)
+        args = [_dev_arg(t, m * self.limbs, self.n, self.word_bits, dev)
+                for t, m in zip((c_hat, a_hat, b_hat), polys)]
+        wp = None if w_hat is None else _dev_arg(w_hat, rots * self.limbs, self.n,
+                                                 self.word_bits, dev)
+        zp = None if c0_hat is None else _dev_arg(c0_hat, batch * self.q_limbs, self.n,
+                                                  self.word_bits, dev)
+        karr = (ctypes.c_uint32 * max(1, rots))(*k)
+        self._check(self._c.apply_device(self._h, *args, wp, zp, karr, rots, batch, terms, comps,
+                                         dev, stream or None))
+
+    def apply(self, a_hat, b_hat, k, w_hat=None, c0_hat=None) -> np.ndarray:
+        """a_hat of shape [batch, terms, L + K, n]; b_hat of shape [rots, comps, terms, L + K, n]
+        with rots = len(k); w_hat of shape [rots, L + K, n] or None; c0_hat of shape [batch, L, n]
+        or None.  Returns c_hat of shape [batch, comps, L + K, n]."""
+        a_hat = np.ascontiguousarray(a_hat, dtype=self.io_dtype)
+        b_hat = np.ascontiguousarray(b_hat, dtype=self.io_dtype)
+        k = [int(x) for x in k]
+        if a_hat.ndim != 4 or a_hat.shape[2:] != (self.limbs, self.n) or a_hat.shape[1] == 0:
+            raise ValueError(f"apply: a_hat must have shape [batch, terms > 0, {self.limbs}, {self.n}]")
+        if b_hat.ndim != 5 or b_hat.shape[-3:] != a_hat.shape[1:] or b_hat.shape[0] != len(k):
+            raise ValueError("apply: b_hat must have shape [len(k), comps, terms, L + K, n]")
+        rots, comps = b_hat.shape[:2]
+        batch = a_hat.shape[0]
+        wp = zp = None
+        if w_hat is not None:
+            w_hat = np.ascontiguousarray(w_hat, dtype=self.io_dtype)
+            if w_hat.shape != (rots, self.limbs, self.n):
+                raise ValueError("apply: w_hat must have shape [len(k), L + K, n]")
+            wp = w_hat.ctypes.data
+        if c0_hat is not None:
+            c0_hat = np.ascontiguousarray(c0_hat, dtype=self.io_dtype)
+            if c0_hat.shape != (batch, self.q_limbs, self.n):
+                raise ValueError("apply: c0_hat must have shape [batch, L, n]")
+            zp = c0_hat.ctypes.data
+        c = np.empty((batch, comps, self.limbs, self.n), dtype=self.io_dtype)
+        karr = (ctypes.c_uint32 * max(1, rots))(*k)
+        self._check(self._c.apply(self._h, c.ctypes.data, a_hat.ctypes.data, b_hat.ctypes.data,
+                                  wp, zp, karr, rots, batch, a_hat.shape[1], comps))
+        return c
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
