@@ -2055,6 +2055,155 @@ class NttLinTrans(_Handle):
         return c
 
 
+# ---- the product of two ciphertexts on NTT-domain limbs (include/nttmul_ctmul.h) -----------------
+
+CTMUL_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_ctmul.so")
+CTMUL_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_ctmul.h")
+CTMUL_OPS = ("high", "relin")
+
+
+class CtMulInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("q_limbs", ctypes.c_uint32),
+                ("p_limbs", ctypes.c_uint32), ("word_bits", ctypes.c_uint32),
+                ("ndev", ctypes.c_int)]
+
+
+def load_ctmul_library(path: str = CTMUL_LIB_PATH) -> ctypes.CDLL:
+    """Load lib/libnttmul_ctmul.so (include/nttmul_ctmul.h): the ABI and kernels of
+    libnttmul_lintrans.so plus the ciphertext product.  The other loaders are unaffected."""
+    return _load_limb_library(path, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn, _bind_hoist,
+                              _bind_mdntt, _bind_ksntt, _bind_lintrans, _bind_ctmul)
+
+
+def _bind_ctmul(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    _bind_handle(lib, "nttmul_ctmul", CtMulInfo, [u64p, u32, u64p, u32])
+    lib.nttmul_ctmul_high_device.argtypes = [vp, vp, vp, vp, sz, u32, i32, vp]
+    lib.nttmul_ctmul_high.argtypes = [vp, vp, vp, vp, sz, u32]
+    lib.nttmul_ctmul_relin_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, u32, u32, i32, vp]
+    lib.nttmul_ctmul_relin.argtypes = [vp, vp, vp, vp, vp, vp, sz, u32, u32]
+    lib.nttmul_ctmul_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
+
+
+def ctmul_exported_symbols() -> list:
+    """Function names declared in include/nttmul_ctmul.h."""
+    return _header_symbols(CTMUL_HEADER_PATH, "nttmul_ctmul_")
+
+
+class NttCtMul(_Handle):
+    """nttmul_ctmul: the bases Q = q (L primes) and P = p (K primes), disjoint and of one word
+    class, for one degree n in 256 .. 65536 (include/nttmul_ctmul.h).  Every limb of every
+    operand is in NTT order, as RnsContext / RnsMpContext.forward writes it.  x_hat and y_hat hold
+    `pairs` ciphertexts (c_0, c_1) over Q per batch entry, [batch, pairs, 2, L, n]; the same array
+    for both is the square.
+
+    high is the s^2 term, d2_hat[p] = sum_s x_hat[p][s][1] o y_hat[p][s][1], what
+    NttKeySwitch.modup reads.  relin is its key switch plus P (d0, d1) in Q u P,
+    c_hat[p][i] = sum_t up_hat[p][t] o key_hat[i][t] + P e_i[p], with e_0 = sum_s x[s][0] o y[s][0]
+    and e_1 = sum_s (x[s][0] o y[s][1] + x[s][1] o y[s][0]); its c_hat is what NttModDown.moddown
+    reads with batch * 2 polynomials.
+
+    Caller memory: operands need the alignment of their word only; the output must overlap no
+    input (inputs may alias each other); high writes exactly batch * L * n words and relin
+    batch * 2 * (L + K) * n, and neither writes an input."""
+
+    _PREFIX = "nttmul_ctmul"
+    _NAME_CAP = 256
+
+    def __init__(self, n: int, q, p, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False, lib_path: Optional[str] = None):
+        q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
+        prm.ndev, prm.first_dev = ndev, first_dev
+        info = CtMulInfo()
+        lib = load_ctmul_library(lib_path) if lib_path else load_ctmul_library()
+        self._open(lib, info, prm, qa, len(q), pa, len(p))  # self.info
+        self.n, self.word_bits = info.n, info.word_bits
+        self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
+        self.limbs = info.q_limbs + info.p_limbs
+        self.q, self.p = tuple(q), tuple(p)
+        self.first_dev = first_dev
+
+    def kernel_name(self, op) -> str:
+        """nttmul_ctmul_kernel_name for op 0..1 or "high" / "relin", e.g.
+        "k_ctmul_relin<Arith64,u64>"."""
+        op = CTMUL_OPS.index(op) if isinstance(op, str) else int(op)
+        buf = ctypes.create_string_buffer(self._NAME_CAP)
+        st = self._c.kernel_name(self._h, op, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def _pair_args(self, x_hat, y_hat, batch, pairs, dev):
+        polys = batch * pairs * 2 * self.q_limbs
+        xp = _dev_arg(x_hat, polys, self.n, self.word_bits, dev)
+        yp = xp if y_hat is x_hat else _dev_arg(y_hat, polys, self.n, self.word_bits, dev)
+        return xp, yp
+
+    def high_device(self, d2_hat, x_hat, y_hat, batch: int, pairs: int,
+                    dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        x_hat, y_hat [batch][pairs][2][L][n] -> d2_hat [batch][L][n]."""
+        dev = self.first_dev if dev is None else dev
+        out = _dev_arg(d2_hat, batch * self.q_limbs, self.n, self.word_bits, dev)
+        xp, yp = self._pair_args(x_hat, y_hat, batch, pairs, dev)
+        self._check(self._c.high_device(self._h, out, xp, yp, batch, pairs, dev, stream or None))
+
+    def relin_device(self, c_hat, up_hat, key_hat, x_hat, y_hat, batch: int, pairs: int,
+                     terms: int, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        up_hat [batch][terms][L + K][n], key_hat [2][terms][L + K][n], x_hat and y_hat
+        [batch][pairs][2][L][n] -> c_hat [batch][2][L + K][n]."""
+        dev = self.first_dev if dev is None else dev
+        polys = (batch * 2, batch * terms, 2 * terms)
+        args = [_dev_arg(t, m * self.limbs, self.n, self.word_bits, dev)
+                for t, m in zip((c_hat, up_hat, key_hat), polys)]
+        xp, yp = self._pair_args(x_hat, y_hat, batch, pairs, dev)
+        self._check(self._c.relin_device(self._h, *args, xp, yp, batch, pairs, terms, dev,
+                                         stream or None))
+
+    def _host_pairs(self, what, x_hat, y_hat):
+        same = y_hat is x_hat
+        x_hat = np.ascontiguousarray(x_hat, dtype=self.io_dtype)
+        y_hat = x_hat if same else np.ascontiguousarray(y_hat, dtype=self.io_dtype)
+        if x_hat.ndim != 5 or x_hat.shape[2:] != (2, self.q_limbs, self.n) or x_hat.shape[1] == 0:
+            raise ValueError(f"{what}: x_hat must have shape [batch, pairs > 0, 2, "
+                             f"{self.q_limbs}, {self.n}]")
+        if y_hat.shape != x_hat.shape:
+            raise ValueError(f"{what}: y_hat must have x_hat's shape")
+        return x_hat, y_hat
+
+    def high(self, x_hat, y_hat) -> np.ndarray:
+        """x_hat, y_hat of shape [batch, pairs, 2, L, n] (the same array: the square).  Returns
+        d2_hat of shape [batch, L, n]."""
+        x_hat, y_hat = self._host_pairs("high", x_hat, y_hat)
+        batch, pairs = x_hat.shape[:2]
+        d2 = np.empty((batch, self.q_limbs, self.n), dtype=self.io_dtype)
+        self._check(self._c.high(self._h, d2.ctypes.data, x_hat.ctypes.data, y_hat.ctypes.data,
+                                 batch, pairs))
+        return d2
+
+    def relin(self, up_hat, key_hat, x_hat, y_hat) -> np.ndarray:
+        """up_hat of shape [batch, terms, L + K, n]; key_hat of shape [2, terms, L + K, n]; x_hat,
+        y_hat of shape [batch, pairs, 2, L, n].  Returns c_hat of shape [batch, 2, L + K, n]."""
+        up_hat = np.ascontiguousarray(up_hat, dtype=self.io_dtype)
+        key_hat = np.ascontiguousarray(key_hat, dtype=self.io_dtype)
+        x_hat, y_hat = self._host_pairs("relin", x_hat, y_hat)
+        if up_hat.ndim != 4 or up_hat.shape[2:] != (self.limbs, self.n) or up_hat.shape[1] == 0:
+            raise ValueError(f"relin: up_hat must have shape [batch, terms > 0, {self.limbs}, "
+                             f"{self.n}]")
+        if key_hat.shape != (2,) + up_hat.shape[1:]:
+            raise ValueError("relin: key_hat must have shape [2, terms, L + K, n]")
+        if x_hat.shape[0] != up_hat.shape[0]:
+            raise ValueError("relin: x_hat and up_hat must have the same batch")
+        batch, pairs = x_hat.shape[:2]
+        c = np.empty((batch, 2, self.limbs, self.n), dtype=self.io_dtype)
+        self._check(self._c.relin(self._h, c.ctypes.data, up_hat.ctypes.data, key_hat.ctypes.data,
+                                  x_hat.ctypes.data, y_hat.ctypes.data, batch, pairs,
+                                  up_hat.shape[1]))
+        return c
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
