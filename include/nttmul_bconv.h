@@ -12,6 +12,8 @@
  * limbs as in nttmul_rns.h, [batch][limbs][n], in coefficient (standard) order: these are not
  * transforms.  Every input word is canonical (below its own limb's modulus) and so is every
  * output word.
+ * The moduli of a context may be of any sizes within their word class and in any order
+ * (tests/test_gpu_bases.py).
  *
  *   convert   in [batch][L][n] -> out [batch][K][n], the fast base conversion with unreduced alpha:
  *               y_i          = in[p][i][k] (Bh_i^-1 mod b_i) mod b_i

@@ -14,6 +14,8 @@
  * limb of every operand is a transform: bit-reversed NTT order, canonical words, what
  * nttmul_rns_forward / nttmul_rnsmp_forward write for that limb's modulus.  The context needs no
  * twiddles, no digit width and no scratch.
+ * The moduli of a context may be of any sizes within their word class and in any order
+ * (tests/test_gpu_bases.py).
  *
  * A ciphertext is its two components over Q, [2][L][n]; x_hat and y_hat hold `pairs` of them per
  * batch entry, [batch][pairs][2][L][n].  pairs = 1 is the plain product; pairs > 1 is a dot

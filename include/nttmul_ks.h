@@ -17,6 +17,8 @@
  * Operands are polynomial-major arrays of residue limbs in coefficient (standard) order: these
  * are not transforms.  Every input word is canonical (below its own limb's modulus) and so is
  * every output word.
+ * The moduli of a context may be of any sizes within their word class and in any order
+ * (tests/test_gpu_bases.py).
  *
  *   modup    in [batch][L][n] -> out [batch][dnum][L + K][n]
  *              y_i             = in[p][i][k] (Dh_i^-1 mod q_i) mod q_i             for i in D_d

@@ -15,6 +15,8 @@
  * then P, M = L + K limbs m_0 .. m_{M-1}.  Every limb of every operand is a transform:
  * bit-reversed NTT order, canonical words, what nttmul_rns_forward / nttmul_rnsmp_forward write
  * for that limb's modulus.
+ * The moduli of a context may be of any sizes within their word class and in any order
+ * (tests/test_gpu_bases.py).
  *
  *   modup  x_hat [batch][L][n] -> up_hat [batch][dnum][M][n]
  *            y_i             = INTT_{q_i}(x_hat[p][i]) (Dh_i^-1 mod q_i) mod q_i      coefficient order

@@ -13,6 +13,8 @@
  * limb of every operand is a transform: bit-reversed NTT order, canonical words, what
  * nttmul_rns_forward / nttmul_rnsmp_forward write for that limb's modulus.  The context needs no
  * twiddles and no digit width.
+ * The moduli of a context may be of any sizes within their word class and in any order
+ * (tests/test_gpu_bases.py).
  *
  *   apply  a_hat  [batch][terms][M][n]         the raised digits (nttmul_ksntt_modup's up_hat)
  *          b_hat  [rots][comps][terms][M][n]   the keys, shared by the batch (nttmul_ksntt_mac's)

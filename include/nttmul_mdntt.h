@@ -13,6 +13,8 @@
  * Ph_j = P / p_j.  Every limb of the input is a transform: bit-reversed NTT order, canonical
  * words, what nttmul_rns_forward / nttmul_rnsmp_forward write for that limb's modulus.  So is
  * every limb of the output.
+ * The moduli of a context may be of any sizes within their word class and in any order
+ * (tests/test_gpu_bases.py).
  *
  *   moddown  x_hat [batch][L + K][n] -> out [batch][L][n]
  *              y_j       = INTT_{p_j}(x_hat[p][L + j]) (Ph_j^-1 mod p_j) mod p_j     coefficient order

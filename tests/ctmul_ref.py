@@ -137,14 +137,16 @@ def chain_bound():
     return (HC.CHAIN_SHAPE[1] + 1) * (1 + HC.CHAIN_H)
 
 
-def chain_inputs(n, bits, pairs=1, batch=None):
+def chain_inputs(n, bits, pairs=1, batch=None, bases=None):
     """Seeded inputs of the multiplication on hoist_cases.CHAIN_SHAPE: q, p, alpha, a ternary s of
     weight CHAIN_H, ss = s s as signed integers, the zero-noise key (b, a) [2, dnum, L + K, n] that
-    switches s s to s, and random words x, y [batch, pairs, 2, L, n] over Q (coefficient order)."""
+    switches s s to s, and random words x, y [batch, pairs, 2, L, n] over Q (coefficient order).  bases: (q, p) of the
+    shape's L and K limbs in place of ks_ref.bases(bits, L, K)."""
     L, K, alpha = HC.CHAIN_SHAPE
     batch = HC.CHAIN_BATCH if batch is None else batch
     dt = np.uint32 if bits == 32 else np.uint64
-    q, p = ks_ref.bases(bits, L, K)
+    q, p = ks_ref.bases(bits, L, K) if bases is None else bases
+    assert (len(q), len(p)) == (L, K)
     rng = np.random.default_rng(3 * n + bits + pairs)
     s = ks_ref.ternary(rng, n, HC.CHAIN_H)
     ss = signed_square(s)
@@ -169,13 +171,13 @@ def signed_square(s):
 
 
 @lru_cache(maxsize=None)
-def chain(n, bits, pairs=1):
+def chain(n, bits, pairs=1, bases=None):
     """The multiplication in Python integers at small n: chain_inputs plus x_hat, y_hat, key_hat,
     d2_hat = high, up_hat = forward(modup(inverse(d2_hat))), mid = relin [batch, 2, L + K, n]
     (NTT order), out = moddown of its inverse [batch, 2, L, n] (coefficient order), and
     d = (d0, d1, d2) [3, batch, L, n], the inverse of the pointwise products (coefficient
     order)."""
-    ch = chain_inputs(n, bits, pairs)
+    ch = chain_inputs(n, bits, pairs, bases=bases)
     q, p = ch["q"], ch["p"]
     ext, L = q + p, len(q)
     dt = ch["x"].dtype

@@ -84,17 +84,19 @@ def rotate_signed(s, k):
 
 
 @lru_cache(maxsize=None)
-def chain(n, bits):
+def chain(n, bits, bases=None):
     """The hoisted key switch of tests/hoist_cases.py CHAIN at (n, bits), every stage in Python
     integers on seeded inputs: x [batch, L, n] is the c_1 part of ciphertexts under s2; for each
     rotation k_r a zero-noise key switches sigma_k(s2) to s.  Returns a dict of the inputs (q, p,
     alpha, ks, s, s2, x, key [rots, 2, dnum, L + K, n]) and of every stage: up = modup(x), up_hat
     and key_hat = forward, mid = hoist_ntt [batch, rots, 2, L + K, n], out = moddown
-    [batch, rots, 2, L, n]."""
+    [batch, rots, 2, L, n].  bases: (q, p) of the shape's L and K limbs in place of
+    ks_ref.bases(bits, L, K)."""
     L, K, alpha = C.CHAIN_SHAPE
     batch, h, rots = C.CHAIN_BATCH, C.CHAIN_H, C.CHAIN_ROTS
     dt = np.uint32 if bits == 32 else np.uint64
-    q, p = ks_ref.bases(bits, L, K)
+    q, p = ks_ref.bases(bits, L, K) if bases is None else bases
+    assert (len(q), len(p)) == (L, K)
     ext, dn = q + p, -(-L // alpha)
     ks = C.draw(n, rots, 1)                                        # 5, 25, 2n - 1
     rng = np.random.default_rng(n + bits)

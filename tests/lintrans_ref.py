@@ -102,13 +102,13 @@ def weights_hat(ws, moduli, n, dtype):
 
 
 @lru_cache(maxsize=None)
-def chain(n, bits):
+def chain(n, bits, bases=None):
     """The linear transform sum_r w_r sigma_{k_r}(.) of the ciphertexts (c0, x) under s2 of
     hoist_ref.chain(n, bits), with its keys: a seeded c0 [batch, L, n], seeded weights, and every
     stage in Python integers.  Returns hoist_ref.chain's dict extended by c0, c0_hat, ws (signed
     lists), w_hat [rots, L + K, n], mid_lt = apply [batch, 2, L + K, n] (NTT order) and out_lt =
-    moddown of its inverse [batch, 2, L, n] (coefficient order)."""
-    ch = dict(H.chain(n, bits))
+    moddown of its inverse [batch, 2, L, n] (coefficient order).  bases: as hoist_ref.chain's."""
+    ch = dict(H.chain(n, bits, bases))
     q, p = ch["q"], ch["p"]
     ext, L = q + p, len(q)
     dt = ch["x"].dtype
