@@ -52,7 +52,8 @@
  * Out of scope here:
  *   - exact conversion, that is the alpha correction (floating-point as Halevi-Polyakov-Shoup, or
  *     a redundant modulus);
- *   - rounding instead of flooring in moddown;
+ *   - rounding instead of flooring in moddown (for NTT-domain limbs both are nttmul_xconv.h,
+ *     lib/libnttmul_xconv.so);
  *   - NTT-domain inputs, or a fused inverse transform -> convert -> forward transform pipeline
  *     (for ModDown that is nttmul_mdntt.h, lib/libnttmul_mdntt.so);
  *   - n > 4096, the class 2^31 <= q < 2^32, and 64-bit storage of 32-bit limbs;

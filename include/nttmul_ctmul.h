@@ -85,7 +85,8 @@
  *   - a key, or a plaintext operand, per batch entry;
  *   - ciphertext x plaintext (a per-limb pointwise product, no key);
  *   - three-component ciphertexts as inputs;
- *   - rounding in ModDown, and exact conversion (the alpha correction);
+ *   - rounding in ModDown, and exact conversion (the alpha correction): both are nttmul_xconv.h,
+ *     lib/libnttmul_xconv.so, whose moddown reads what this header's calls write;
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC), the class 2^31 <= q < 2^32;
  *   - a chunked or multi-device host path (the host forms below are deliberately simple);
  *   - a bench.py mode (tools/bench_ctmul.py measures these calls).

@@ -79,7 +79,8 @@
  * *_device calls: synchronise them first.
  *
  * Out of scope here:
- *   - rounding in ModDown, and exact conversion (the alpha correction);
+ *   - rounding in ModDown, and exact conversion (the alpha correction): both are nttmul_xconv.h,
+ *     lib/libnttmul_xconv.so, whose moddown reads what this header's calls write;
  *   - a b_hat per batch entry, or more than NTTMUL_MACN_MAX_COMPS components;
  *   - summing the rotations before ModDown (rotate-and-sum in Q u P): nttmul_lintrans.h's
  *     nttmul_lintrans_apply, in lib/libnttmul_lintrans.so;

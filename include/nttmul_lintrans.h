@@ -70,7 +70,8 @@
  *   - a b_hat or a w_hat per batch entry;
  *   - more than NTTMUL_MACN_MAX_COMPS components;
  *   - BSGS giant steps: a second apply over the first's ModDown output, nothing new;
- *   - rounding in ModDown, and exact conversion (the alpha correction);
+ *   - rounding in ModDown, and exact conversion (the alpha correction): both are nttmul_xconv.h,
+ *     lib/libnttmul_xconv.so, whose moddown reads what this header's calls write;
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC), the class 2^31 <= q < 2^32;
  *   - a chunked or multi-device host path (the host form below is deliberately simple);
  *   - a bench.py mode (tools/bench_lintrans.py measures this call).

@@ -61,12 +61,13 @@
  * the streams passed to the *_device calls: synchronise them first.
  *
  * Out of scope here:
- *   - rounding instead of flooring (add floor(P / 2) before the call for it);
+ *   - rounding instead of flooring (nttmul_xconv.h, lib/libnttmul_xconv.so, has the rounded
+ *     ModDown on the same operands);
  *   - a P part in coefficient order, or a coefficient-order output;
  *   - NTT-domain output of nttmul_*_macn_ntt / nttmul_*_hoist_ntt (nttmul_ksntt.h,
  *     lib/libnttmul_ksntt.so, has the hoisted mac with NTT-domain output and the ModUp in front of
  *     it, so that the whole key switch ends here);
- *   - exact conversion (the alpha correction);
+ *   - exact conversion (the alpha correction: nttmul_xconv.h as well);
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC), the class 2^31 <= q < 2^32;
  *   - a chunked or multi-device host path (the host form below is deliberately simple);
  *   - a bench.py mode (tools/bench_mdntt.py measures this call).

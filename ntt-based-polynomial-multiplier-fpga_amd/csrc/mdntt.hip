@@ -158,6 +158,34 @@ hipError_t launch_mdntt_inverse(const MdTables &T, const void *x_hat, size_t cnt
                            : dispatch_inv<Arith64, uint64_t>(T, x_hat, cnt, scr, E);
 }
 
+template <class A, class IO>
+static hipError_t dispatch_rows(const MdTables &T, void *out, const void *xh, size_t cnt,
+                                void *const *scr, const Emit &E) {
+  using W = typename A::word;
+  const auto rows = [&](auto l1) {
+    constexpr int L1 = decltype(l1)::value;
+    return emit_q_fastest(E, md_name<A, IO>("k_mdntt_rows", L1), k_mdntt_rows<A, IO, L1>,
+                          cnt << L1, T.L, (const KParams<A> *)T.tab_fwd, (const TwPair<W> *)T.tw,
+                          (const BconvTo<W> *)T.to, (const W *)scr[kMdT], (const IO *)xh, (IO *)out,
+                          cnt << L1, T.L, T.K);
+  };
+  switch (T.logn) {
+    case 13: return rows(std::integral_constant<int, 1>{});
+    case 14: return rows(std::integral_constant<int, 2>{});
+    case 15: return rows(std::integral_constant<int, 3>{});
+    case 16: return rows(std::integral_constant<int, 4>{});
+    default: return hipErrorNotSupported;
+  }
+}
+
+hipError_t launch_mdntt_rows(const MdTables &T, void *out, const void *x_hat, size_t cnt,
+                             void *const *scr, hipStream_t s, std::string *describe) {
+  if (!T.L || !T.K) return hipErrorInvalidValue;
+  const Emit E{s, describe};
+  return T.word_bits == 32 ? dispatch_rows<Arith32P, uint32_t>(T, out, x_hat, cnt, scr, E)
+                           : dispatch_rows<Arith64, uint64_t>(T, out, x_hat, cnt, scr, E);
+}
+
 hipError_t launch_mdntt(const MdTables &T, void *out, const void *x_hat, size_t cnt,
                         void *const *scr, hipStream_t s) {
   return dispatch_words(T, out, x_hat, cnt, scr, Emit{s, nullptr});

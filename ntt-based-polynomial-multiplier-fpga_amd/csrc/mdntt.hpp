@@ -34,6 +34,12 @@ hipError_t launch_mdntt(const MdTables &T, void *out, const void *x_hat, size_t 
 // With `describe` set nothing is launched and the kernels' names are appended to it.
 hipError_t launch_mdntt_inverse(const MdTables &T, const void *x_hat, size_t cnt,
                                 void *const *scr, hipStream_t s, std::string *describe);
+// The last launch of launch_mdntt above n = 4096 alone: k_mdntt_rows on the column-passed sums in
+// scr[kMdT] ([cnt][L][n], lazy words), with the epilogue's factor read from T.to.  What the
+// rounded ModDown of include/nttmul_xconv.h ends in (xconv.hip), its T.to carrying t P^-1.
+// With `describe` set nothing is launched and the kernel's name is appended to it.
+hipError_t launch_mdntt_rows(const MdTables &T, void *out, const void *x_hat, size_t cnt,
+                             void *const *scr, hipStream_t s, std::string *describe);
 // The kernels launch_mdntt launches for T, joined by " + ": the dry run of the launching
 // statements themselves (kernels_dev.hpp Emit)
 hipError_t describe_mdntt(const MdTables &T, std::string *out);

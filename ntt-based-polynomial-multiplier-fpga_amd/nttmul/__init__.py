@@ -2204,6 +2204,157 @@ class NttCtMul(_Handle):
         return c
 
 
+# ---- exact base extension and rounded ModDown (include/nttmul_xconv.h) ---------------------------
+
+XCONV_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_xconv.so")
+XCONV_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_xconv.h")
+XCONV_OPS = ("extend", "moddown")
+
+
+class XConvInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("q_limbs", ctypes.c_uint32),
+                ("p_limbs", ctypes.c_uint32), ("word_bits", ctypes.c_uint32),
+                ("ndev", ctypes.c_int), ("scratch_mb", ctypes.c_uint32),
+                ("band_log2", ctypes.c_uint32), ("scale", ctypes.c_uint64)]
+
+
+def load_xconv_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_xconv.so (include/nttmul_xconv.h): the ABI and kernels of
+    libnttmul_ctmul.so plus the exact base extension and the rounded ModDown.  The other loaders
+    are unaffected."""
+    return _load_limb_library(XCONV_LIB_PATH, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn,
+                              _bind_hoist, _bind_mdntt, _bind_ksntt, _bind_lintrans, _bind_ctmul,
+                              _bind_xconv)
+
+
+def _bind_xconv(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u64, u64p = ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
+    _bind_handle(lib, "nttmul_xconv", XConvInfo, [u64p, u32, u64p, u32, u64])
+    for op in XCONV_OPS:
+        getattr(lib, f"nttmul_xconv_{op}_device").argtypes = [vp, vp, vp, sz, i32, vp]
+        getattr(lib, f"nttmul_xconv_{op}").argtypes = [vp, vp, vp, sz]
+    lib.nttmul_xconv_plan.argtypes = [ctypes.POINTER(_Params), sz, u64p, u32, u64p, u32, u64,
+                                      vp, vp, vp, vp]
+    lib.nttmul_xconv_kernel_name.argtypes = [vp, i32, ctypes.c_char_p, sz]
+
+
+def xconv_exported_symbols() -> list:
+    """Function names declared in include/nttmul_xconv.h."""
+    return _header_symbols(XCONV_HEADER_PATH, "nttmul_xconv_")
+
+
+def xconv_plan(n: int, q, p, scale: int = 1, flags: int = 0):
+    """nttmul_xconv_plan, without a device: (yscale, w_ext, w_md, v) as lists of Python integers.
+    yscale[j] = t Ph_j^-1 mod p_j; w_ext[j][l] = Ph_j mod q_l for j < K and w_ext[K][l] = -P mod
+    q_l; w_md[j][l] = Ph_j t^-1 mod q_l and w_md[K][l] = -P t^-1 mod q_l; v[l] = t P^-1 mod q_l.
+    Raises NttmulError with the status nttmul_xconv_create would return for these arguments before
+    any device access."""
+    lib = load_xconv_library()
+    q, p, prm, qa, pa = _ks_bases(n, q, p, flags)
+    L, K = len(q), len(p)
+    if not 0 <= scale < 1 << 64:
+        raise NttmulError(NTTMUL_EINVAL, lib.nttmul_strerror(NTTMUL_EINVAL).decode())
+    sizes = (K, (K + 1) * L, (K + 1) * L, L)
+    t = [(ctypes.c_uint64 * max(1, k))() for k in sizes]
+    st = lib.nttmul_xconv_plan(ctypes.byref(prm), ctypes.sizeof(prm), qa, L, pa, K, scale,
+                               *(ctypes.addressof(x) for x in t))
+    if st != NTTMUL_OK:
+        raise NttmulError(st, lib.nttmul_strerror(st).decode())
+    yscale, w_ext, w_md, v = (list(x[:k]) for x, k in zip(t, sizes))
+    rows = lambda flat, width: [flat[i:i + width] for i in range(0, len(flat), width)]
+    return yscale, rows(w_ext, L), rows(w_md, L), v
+
+
+class NttExactConv(_Handle):
+    """nttmul_xconv: the bases Q = q (L primes) and P = p (K primes), disjoint and of one word
+    class, and a scale t, for one degree n in 256 .. 65536 (include/nttmul_xconv.h).  Every limb
+    of every operand is in NTT order, as RnsContext / RnsMpContext.forward writes it.
+
+    extend maps p_hat [batch, K, n] over P to [batch, L, n] over Q: the centred representative in
+    [-(P-1)/2, (P-1)/2] of t * (the input's CRT value) mod P, reduced modulo each q_l.  scale = 1
+    is the exact basis extension, K = 1 is ModRaise.  moddown maps x_hat [batch, L + K, n] to
+    [batch, L, n]: round(t X / P) mod q_l for the CRT value X over Q u P; scale = 1 is the rounded
+    ModDown (NttModDown.moddown floors).
+
+    Both are exact for every coefficient with |frac(phi) - 1/2| > eps, phi = sum_j y_j / p_j and
+    eps = K * 2**-info.band_log2 (self.eps as a Fraction); inside that band the result is the exact
+    value or its neighbour by one P, the same in every limb.
+
+    Caller memory: operands need the alignment of their word only; out must not overlap the
+    input; a call writes exactly batch * L * n words of out and never writes the input.
+
+    close() waits for the last use of the context's scratch, not for the streams passed to the
+    *_device calls: synchronise them first."""
+
+    _PREFIX = "nttmul_xconv"
+    _OPS = XCONV_OPS
+    _NAME_CAP = 256
+
+    def __init__(self, n: int, q, p, scale: int = 1, ndev: int = 1, first_dev: int = 0,
+                 validate: bool = False, cyclic: bool = False, share_devices: bool = False,
+                 scratch_mb: int = 0):
+        q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
+        prm.ndev, prm.first_dev, prm.scratch_mb = ndev, first_dev, scratch_mb
+        info = XConvInfo()
+        lib = load_xconv_library()
+        if not 0 <= scale < 1 << 64:
+            raise NttmulError(NTTMUL_EINVAL, lib.nttmul_strerror(NTTMUL_EINVAL).decode())
+        self._open(lib, info, prm, qa, len(q), pa, len(p), scale)
+        self.n, self.word_bits = info.n, info.word_bits
+        self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
+        self.q, self.p, self.scale = tuple(q), tuple(p), info.scale
+        self.band_log2 = info.band_log2
+        self.first_dev = first_dev
+
+    @property
+    def eps(self):
+        """The guard band of a, K 2^-band_log2, as a fractions.Fraction."""
+        from fractions import Fraction
+        return Fraction(self.p_limbs, 1 << self.band_log2)
+
+    def kernel_name(self, op) -> str:
+        """nttmul_xconv_kernel_name for op 0..1 or "extend" / "moddown", e.g.
+        "k_mdntt_inv<Arith32P,u32,12> + k_xconv_fwd<Arith32P,u32,12,1>"."""
+        return self._kernel_name(op)
+
+    def _in_limbs(self, op: str) -> int:
+        return self.p_limbs if op == "extend" else self.q_limbs + self.p_limbs
+
+    def _device(self, op, out, src, batch, dev, stream):
+        dev = self.first_dev if dev is None else dev
+        args = [_dev_arg(t, batch * k, self.n, self.word_bits, dev)
+                for t, k in zip((out, src), (self.q_limbs, self._in_limbs(op)))]
+        self._check(getattr(self._c, f"{op}_device")(self._h, *args, batch, dev, stream or None))
+
+    def _host(self, op, src) -> np.ndarray:
+        limbs = self._in_limbs(op)
+        src = np.ascontiguousarray(src, dtype=self.io_dtype)
+        if src.ndim != 3 or src.shape[1:] != (limbs, self.n):
+            raise ValueError(f"{op}: the input must have shape [batch, {limbs}, {self.n}]")
+        out = np.empty((src.shape[0], self.q_limbs, self.n), dtype=self.io_dtype)
+        self._check(getattr(self._c, op)(self._h, out.ctypes.data, src.ctypes.data, src.shape[0]))
+        return out
+
+    def extend_device(self, out, p_hat, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        p_hat [batch][K][n] -> out [batch][L][n]."""
+        self._device("extend", out, p_hat, batch, dev, stream)
+
+    def moddown_device(self, out, x_hat, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        x_hat [batch][L + K][n] -> out [batch][L][n]."""
+        self._device("moddown", out, x_hat, batch, dev, stream)
+
+    def extend(self, p_hat) -> np.ndarray:
+        """p_hat of shape [batch, K, n]; returns [batch, L, n]."""
+        return self._host("extend", p_hat)
+
+    def moddown(self, x_hat) -> np.ndarray:
+        """x_hat of shape [batch, L + K, n]; returns [batch, L, n]."""
+        return self._host("moddown", x_hat)
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
