@@ -93,23 +93,84 @@ int run_high(nttmul_ctmul *h, CtDev &d, void *d2, const void *x, const void *y, 
   return e == hipSuccess ? NTTMUL_OK : fail(h->err, e, "high launch");
 }
 
+// V: key_hat is viewed (ctmul.hpp CtViewed), its check and the launch are V's
 int run_relin(nttmul_ctmul *h, CtDev &d, void *c, const void *up, const void *key, const void *x,
-              const void *y, size_t batch, uint32_t pairs, uint32_t terms, hipStream_t s) {
+              const void *y, size_t batch, uint32_t pairs, uint32_t terms, hipStream_t s,
+              const CtViewed *V = nullptr) {
   if (!batch) return NTTMUL_OK;
   const CtPlan &P = h->plan;
   if (P.flags & NTTMUL_FLAG_VALIDATE) {
     size_t words[4];
     ctmul_relin_words(P.L, P.K, P.n, batch, pairs, terms, words);
     if (const int st = check_range(h->err, d.base.flag, d.base.q, P.L + P.K, P.logn, P.word_bits,
-                                   up, words[1], key, words[2], kRangeMsg, s))
+                                   up, words[1], key, V ? 0 : words[2], kRangeMsg, s))
       return st;
+    if (V)
+      if (const int st = V->check(h->err, d.base.flag, d.base.q, P.word_bits, key, *V->addr, 2,
+                                  terms, true, kRangeMsg, s))
+        return st;
     if (const int st = check_pairs(h, d, x, y, words[3], s)) return st;
   }
-  const hipError_t e = launch_ctmul_relin(view(h, d), c, up, key, x, y, batch, pairs, terms, s);
+  const hipError_t e =
+      V ? V->launch(view(h, d), c, up, key, x, y, batch, pairs, terms, *V->addr, s)
+        : launch_ctmul_relin(view(h, d), c, up, key, x, y, batch, pairs, terms, s);
   return e == hipSuccess ? NTTMUL_OK : fail(h->err, e, "relin launch");
 }
 
+// nttmul_ctmul_relin_device; V: key_hat viewed
+int relin_device(nttmul_ctmul *h, void *c_hat, const void *up_hat, const void *key_hat,
+                 const void *x_hat, const void *y_hat, size_t batch, uint32_t pairs,
+                 uint32_t terms, int dev, void *stream, const CtViewed *V) {
+  if (const int st = ctmul_relin_status(h != nullptr, c_hat, up_hat, key_hat, x_hat, y_hat, batch,
+                                        pairs, terms))
+    return st;
+  return on_device(h->err, h->dev, h->ndev, dev, [&](CtDev &d) {
+    return run_relin(h, d, c_hat, up_hat, key_hat, x_hat, y_hat, batch, pairs, terms,
+                     (hipStream_t)stream, V);
+  });
+}
+
+// nttmul_ctmul_relin; V: key_hat viewed, staged whole
+int relin_host(nttmul_ctmul *h, void *c_hat, const void *up_hat, const void *key_hat,
+               const void *x_hat, const void *y_hat, size_t batch, uint32_t pairs, uint32_t terms,
+               const CtViewed *V) {
+  if (const int st = ctmul_relin_status(h != nullptr, c_hat, up_hat, key_hat, x_hat, y_hat, batch,
+                                        pairs, terms))
+    return st;
+  if (!batch) return NTTMUL_OK;
+  CtDev &d = h->dev[0];
+  size_t words[4];
+  ctmul_relin_words(h->plan.L, h->plan.K, h->plan.n, batch, pairs, terms, words);
+  if (V) words[2] = V->key_words;
+  const size_t wb = (size_t)h->plan.word_bits / 8;
+  const bool square = y_hat == x_hat;
+  const Staged ops[5] = {{nullptr, c_hat, words[0] * wb},
+                         {up_hat, nullptr, words[1] * wb},
+                         {key_hat, nullptr, words[2] * wb},
+                         {x_hat, nullptr, words[3] * wb},
+                         {y_hat, nullptr, square ? 0 : words[3] * wb}};
+  DeviceGuard guard;
+  LIMB_TRY(h->err, hipSetDevice(d.base.id));
+  void *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int st = staged_begin(h->err, d.base, "ctmul", ops, 5, buf);
+  if (!st) st = run_relin(h, d, buf[0], buf[1], buf[2], buf[3], square ? buf[3] : buf[4], batch,
+                          pairs, terms, d.base.stream, V);
+  return staged_end(h->err, d.base, "ctmul", ops, 5, buf, st);
+}
+
 }  // namespace
+
+namespace nttmul {
+
+int ctmul_relin_viewed(nttmul_ctmul *h, const CtViewed &V, void *c_hat, const void *up_hat,
+                       const void *key_hat, const void *x_hat, const void *y_hat, size_t batch,
+                       uint32_t pairs, uint32_t terms, int host, int dev, void *stream) {
+  if (host) return relin_host(h, c_hat, up_hat, key_hat, x_hat, y_hat, batch, pairs, terms, &V);
+  return relin_device(h, c_hat, up_hat, key_hat, x_hat, y_hat, batch, pairs, terms, dev, stream,
+                      &V);
+}
+
+}  // namespace nttmul
 
 extern "C" {
 
@@ -201,39 +262,14 @@ int nttmul_ctmul_relin_device(nttmul_ctmul *h, void *c_hat, const void *up_hat,
                               const void *key_hat, const void *x_hat, const void *y_hat,
                               size_t batch, uint32_t pairs, uint32_t terms, int dev,
                               void *stream) {
-  if (const int st = ctmul_relin_status(h != nullptr, c_hat, up_hat, key_hat, x_hat, y_hat, batch,
-                                        pairs, terms))
-    return st;
-  return on_device(h->err, h->dev, h->ndev, dev, [&](CtDev &d) {
-    return run_relin(h, d, c_hat, up_hat, key_hat, x_hat, y_hat, batch, pairs, terms,
-                     (hipStream_t)stream);
-  });
+  return relin_device(h, c_hat, up_hat, key_hat, x_hat, y_hat, batch, pairs, terms, dev, stream,
+                      nullptr);
 }
 
 int nttmul_ctmul_relin(nttmul_ctmul *h, void *c_hat, const void *up_hat, const void *key_hat,
                        const void *x_hat, const void *y_hat, size_t batch, uint32_t pairs,
                        uint32_t terms) {
-  if (const int st = ctmul_relin_status(h != nullptr, c_hat, up_hat, key_hat, x_hat, y_hat, batch,
-                                        pairs, terms))
-    return st;
-  if (!batch) return NTTMUL_OK;
-  CtDev &d = h->dev[0];
-  size_t words[4];
-  ctmul_relin_words(h->plan.L, h->plan.K, h->plan.n, batch, pairs, terms, words);
-  const size_t wb = (size_t)h->plan.word_bits / 8;
-  const bool square = y_hat == x_hat;
-  const Staged ops[5] = {{nullptr, c_hat, words[0] * wb},
-                         {up_hat, nullptr, words[1] * wb},
-                         {key_hat, nullptr, words[2] * wb},
-                         {x_hat, nullptr, words[3] * wb},
-                         {y_hat, nullptr, square ? 0 : words[3] * wb}};
-  DeviceGuard guard;
-  LIMB_TRY(h->err, hipSetDevice(d.base.id));
-  void *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int st = staged_begin(h->err, d.base, "ctmul", ops, 5, buf);
-  if (!st) st = run_relin(h, d, buf[0], buf[1], buf[2], buf[3], square ? buf[3] : buf[4], batch,
-                          pairs, terms, d.base.stream);
-  return staged_end(h->err, d.base, "ctmul", ops, 5, buf, st);
+  return relin_host(h, c_hat, up_hat, key_hat, x_hat, y_hat, batch, pairs, terms, nullptr);
 }
 
 int nttmul_ctmul_kernel_name(const nttmul_ctmul *h, int op, char *buf, size_t cap) {

@@ -33,4 +33,22 @@ hipError_t launch_ctmul_relin(const CtTables &T, void *c_hat, const void *up_hat
 // statement itself
 hipError_t describe_ctmul(const CtTables &T, int op, std::string *out);
 
+// relin with key_hat viewed (ksntt.hpp KsnttViewed's shape): `check` in place of its range check,
+// `launch` in place of launch_ctmul_relin, key_words the whole viewed operand (what the host form
+// stages)
+struct CtViewed {
+  const LevelAddr *addr;
+  size_t key_words;
+  LevelCheck check;
+  hipError_t (*launch)(const CtTables &T, void *c_hat, const void *up_hat, const void *key_hat,
+                       const void *x_hat, const void *y_hat, size_t batch, uint32_t pairs,
+                       uint32_t terms, const LevelAddr &A, hipStream_t s);
+};
+// nttmul_ctmul_relin (host != 0; dev and stream unused) or nttmul_ctmul_relin_device with V for
+// key_hat: the same argument checks, device selection, range checks of the other operands and
+// error text
+int ctmul_relin_viewed(nttmul_ctmul *h, const CtViewed &V, void *c_hat, const void *up_hat,
+                       const void *key_hat, const void *x_hat, const void *y_hat, size_t batch,
+                       uint32_t pairs, uint32_t terms, int host, int dev, void *stream);
+
 }  // namespace nttmul

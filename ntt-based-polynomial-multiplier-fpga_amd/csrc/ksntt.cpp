@@ -169,20 +169,26 @@ int run_modup(nttmul_ksntt *h, KnDev &d, void *up, const void *x_hat, size_t bat
   return st;
 }
 
-// on d, stream s: the range check of both operands over the L + K limbs, then the one launch
+// on d, stream s: the range check of both operands over the L + K limbs, then the one launch.
+// V: b_hat is viewed (ksntt.hpp KsnttViewed), its check and the launch are V's
 int run_mac(nttmul_ksntt *h, KnDev &d, void *c, const void *a, const void *b, const HoistArgs &H,
-            size_t batch, uint32_t terms, hipStream_t s) {
+            size_t batch, uint32_t terms, hipStream_t s, const KsnttViewed *V = nullptr) {
   if (!batch) return NTTMUL_OK;
   const KsPlan &P = h->ks;
   if (P.flags & NTTMUL_FLAG_VALIDATE) {
+    const char *msg = "operand word >= its limb's modulus";
     size_t words[3];
     ksntt_mac_words(P.L + P.K, P.n, batch, terms, H.rots, H.comps, words);
     if (const int st = check_range(h->err, d.base.flag, d.base.q, P.L + P.K, P.logn, P.word_bits,
-                                   a, words[1], b, words[2],
-                                   "operand word >= its limb's modulus", s))
+                                   a, words[1], b, V ? 0 : words[2], msg, s))
       return st;
+    if (V)
+      if (const int st = V->check(h->err, d.base.flag, d.base.q, P.word_bits, b, *V->addr,
+                                  (size_t)H.rots * H.comps, terms, true, msg, s))
+        return st;
   }
-  const hipError_t e = launch_ksntt_mac(view(h, d), c, a, b, H, batch, terms, s);
+  const hipError_t e = V ? V->launch(view(h, d), c, a, b, H, batch, terms, *V->addr, s)
+                         : launch_ksntt_mac(view(h, d), c, a, b, H, batch, terms, s);
   return e == hipSuccess ? NTTMUL_OK : fail(h->err, e, "mac launch");
 }
 
@@ -194,7 +200,47 @@ int mac_call(nttmul_ksntt *h, void *c, const void *a, const void *b, const uint3
                           H->ks.k);
 }
 
+// nttmul_ksntt_mac_device; V: b_hat viewed
+int mac_device(nttmul_ksntt *h, void *c_hat, const void *a_hat, const void *b_hat,
+               const uint32_t *k, uint32_t rots, size_t batch, uint32_t terms, uint32_t comps,
+               int dev, void *stream, const KsnttViewed *V) {
+  HoistArgs H;
+  if (const int st = mac_call(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &H)) return st;
+  return on_device(h->err, h->dev, h->ndev, dev, [&](KnDev &d) {
+    return run_mac(h, d, c_hat, a_hat, b_hat, H, batch, terms, (hipStream_t)stream, V);
+  });
+}
+
+// nttmul_ksntt_mac; V: b_hat viewed, staged whole
+int mac_host(nttmul_ksntt *h, void *c_hat, const void *a_hat, const void *b_hat, const uint32_t *k,
+             uint32_t rots, size_t batch, uint32_t terms, uint32_t comps, const KsnttViewed *V) {
+  HoistArgs H;
+  if (const int st = mac_call(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &H)) return st;
+  if (!batch) return NTTMUL_OK;
+  KnDev &d = h->dev[0];
+  size_t words[3];
+  ksntt_mac_words(h->ks.L + h->ks.K, h->ks.n, batch, terms, rots, comps, words);
+  const size_t wb = (size_t)h->ks.word_bits / 8;
+  const Staged ops[3] = {{nullptr, c_hat, words[0] * wb},
+                         {a_hat, nullptr, words[1] * wb},
+                         {b_hat, nullptr, (V ? V->b_words : words[2]) * wb}};
+  return staged_op(h->err, d.base, "ksntt", ops, 3, [&](void *const *buf) {
+    return run_mac(h, d, buf[0], buf[1], buf[2], H, batch, terms, d.base.stream, V);
+  });
+}
+
 }  // namespace
+
+namespace nttmul {
+
+int ksntt_mac_viewed(nttmul_ksntt *h, const KsnttViewed &V, void *c_hat, const void *a_hat,
+                     const void *b_hat, const uint32_t *k, uint32_t rots, size_t batch,
+                     uint32_t terms, uint32_t comps, int host, int dev, void *stream) {
+  if (host) return mac_host(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &V);
+  return mac_device(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, dev, stream, &V);
+}
+
+}  // namespace nttmul
 
 extern "C" {
 
@@ -296,29 +342,13 @@ int nttmul_ksntt_modup(nttmul_ksntt *h, void *up_hat, const void *x_hat, size_t 
 int nttmul_ksntt_mac_device(nttmul_ksntt *h, void *c_hat, const void *a_hat, const void *b_hat,
                             const uint32_t *k, uint32_t rots, size_t batch, uint32_t terms,
                             uint32_t comps, int dev, void *stream) {
-  HoistArgs H;
-  if (const int st = mac_call(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &H)) return st;
-  return on_device(h->err, h->dev, h->ndev, dev, [&](KnDev &d) {
-    return run_mac(h, d, c_hat, a_hat, b_hat, H, batch, terms, (hipStream_t)stream);
-  });
+  return mac_device(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, dev, stream, nullptr);
 }
 
 int nttmul_ksntt_mac(nttmul_ksntt *h, void *c_hat, const void *a_hat, const void *b_hat,
                      const uint32_t *k, uint32_t rots, size_t batch, uint32_t terms,
                      uint32_t comps) {
-  HoistArgs H;
-  if (const int st = mac_call(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &H)) return st;
-  if (!batch) return NTTMUL_OK;
-  KnDev &d = h->dev[0];
-  size_t words[3];
-  ksntt_mac_words(h->ks.L + h->ks.K, h->ks.n, batch, terms, rots, comps, words);
-  const size_t wb = (size_t)h->ks.word_bits / 8;
-  const Staged ops[3] = {{nullptr, c_hat, words[0] * wb},
-                         {a_hat, nullptr, words[1] * wb},
-                         {b_hat, nullptr, words[2] * wb}};
-  return staged_op(h->err, d.base, "ksntt", ops, 3, [&](void *const *buf) {
-    return run_mac(h, d, buf[0], buf[1], buf[2], H, batch, terms, d.base.stream);
-  });
+  return mac_host(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, nullptr);
 }
 
 int nttmul_ksntt_kernel_name(const nttmul_ksntt *h, int op, uint32_t comps, char *buf,

@@ -3,6 +3,7 @@
 #pragma once
 #include "hoist.hpp"
 #include "mdntt.hpp"
+#include "nttmul_ksntt.h"
 
 namespace nttmul {
 
@@ -35,5 +36,28 @@ hipError_t launch_ksntt_mac(const KsnttTables &T, void *c_hat, const void *a_hat
 // The kernels a sub-batch of `op` launches for T, joined by " + ": the dry run of the launching
 // statements themselves (kernels_dev.hpp Emit)
 hipError_t describe_ksntt(const KsnttTables &T, int op, uint32_t comps, std::string *out);
+
+// A key operand read through a level view (include/nttmul_level.h, lib/libnttmul_level.so): its
+// address arithmetic (level_plan.hpp) and the range check over exactly the words the view selects.
+// level.cpp supplies the functions; they are not in this library.
+struct LevelAddr;
+using LevelCheck = int (*)(char *err, int *flag, const uint64_t *q, int word_bits, const void *op,
+                           const LevelAddr &A, size_t outer, uint32_t terms, bool has_terms,
+                           const char *msg, hipStream_t s);
+// mac with b_hat viewed: `check` in place of the range check of b_hat, `launch` in place of
+// launch_ksntt_mac, b_words the whole viewed operand (what the host form stages)
+struct KsnttViewed {
+  const LevelAddr *addr;
+  size_t b_words;
+  LevelCheck check;
+  hipError_t (*launch)(const KsnttTables &T, void *c_hat, const void *a_hat, const void *b_hat,
+                       const HoistArgs &H, size_t batch, uint32_t terms, const LevelAddr &A,
+                       hipStream_t s);
+};
+// nttmul_ksntt_mac (host != 0; dev and stream unused) or nttmul_ksntt_mac_device with V for b_hat:
+// the same argument checks, device selection, range check of a_hat and error text
+int ksntt_mac_viewed(nttmul_ksntt *h, const KsnttViewed &V, void *c_hat, const void *a_hat,
+                     const void *b_hat, const uint32_t *k, uint32_t rots, size_t batch,
+                     uint32_t terms, uint32_t comps, int host, int dev, void *stream);
 
 }  // namespace nttmul

@@ -74,9 +74,11 @@ int setup_device(nttmul_lintrans *h, LtDev &d) {
 }
 
 // on d (the current device), stream s: the range check of every operand that is given over its
-// limbs, then the one launch
+// limbs, then the one launch.  V: b_hat and w_hat are viewed (lintrans.hpp LtViewed), their checks
+// and the launch are V's
 int run(nttmul_lintrans *h, LtDev &d, void *c, const void *a, const void *b, const void *w,
-        const void *c0, const HoistArgs &H, size_t batch, uint32_t terms, hipStream_t s) {
+        const void *c0, const HoistArgs &H, size_t batch, uint32_t terms, hipStream_t s,
+        const LtViewed *V = nullptr) {
   if (!batch) return NTTMUL_OK;
   const LtPlan &P = h->plan;
   if (P.flags & NTTMUL_FLAG_VALIDATE) {
@@ -84,18 +86,25 @@ int run(nttmul_lintrans *h, LtDev &d, void *c, const void *a, const void *b, con
     lintrans_words(P.L, P.K, P.n, batch, terms, H.rots, H.comps, words);
     const char *msg = "operand word >= its limb's modulus";
     if (const int st = check_range(h->err, d.base.flag, d.base.q, P.L + P.K, P.logn, P.word_bits,
-                                   a, words[1], b, words[2], msg, s))
+                                   a, words[1], b, V ? 0 : words[2], msg, s))
       return st;
+    if (V)
+      if (const int st = V->check(h->err, d.base.flag, d.base.q, P.word_bits, b, *V->addr,
+                                  (size_t)H.rots * H.comps, terms, true, msg, s))
+        return st;
     if (w)
-      if (const int st = check_range(h->err, d.base.flag, d.base.q, P.L + P.K, P.logn,
-                                     P.word_bits, w, words[3], nullptr, 0, msg, s))
+      if (const int st = V ? V->check(h->err, d.base.flag, d.base.q, P.word_bits, w, *V->addr,
+                                      H.rots, 1, false, msg, s)
+                           : check_range(h->err, d.base.flag, d.base.q, P.L + P.K, P.logn,
+                                         P.word_bits, w, words[3], nullptr, 0, msg, s))
         return st;
     if (c0)
       if (const int st = check_range(h->err, d.base.flag, d.base.q, P.L, P.logn, P.word_bits, c0,
                                      words[4], nullptr, 0, msg, s))
         return st;
   }
-  const hipError_t e = launch_lintrans(view(h, d), c, a, b, w, c0, H, batch, terms, s);
+  const hipError_t e = V ? V->launch(view(h, d), c, a, b, w, c0, H, batch, terms, *V->addr, s)
+                         : launch_lintrans(view(h, d), c, a, b, w, c0, H, batch, terms, s);
   return e == hipSuccess ? NTTMUL_OK : fail(h->err, e, "apply launch");
 }
 
@@ -107,7 +116,65 @@ int apply_call(nttmul_lintrans *h, void *c, const void *a, const void *b, const 
                                comps, H->ks.k);
 }
 
+// nttmul_lintrans_apply_device; V: b_hat and w_hat viewed
+int apply_device(nttmul_lintrans *h, void *c_hat, const void *a_hat, const void *b_hat,
+                 const void *w_hat, const void *c0_hat, const uint32_t *k, uint32_t rots,
+                 size_t batch, uint32_t terms, uint32_t comps, int dev, void *stream,
+                 const LtViewed *V) {
+  HoistArgs H;
+  if (const int st = apply_call(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &H))
+    return st;
+  return on_device(h->err, h->dev, h->ndev, dev, [&](LtDev &d) {
+    return run(h, d, c_hat, a_hat, b_hat, w_hat, c0_hat, H, batch, terms, (hipStream_t)stream, V);
+  });
+}
+
+// nttmul_lintrans_apply; V: b_hat and w_hat viewed, staged whole
+int apply_host(nttmul_lintrans *h, void *c_hat, const void *a_hat, const void *b_hat,
+               const void *w_hat, const void *c0_hat, const uint32_t *k, uint32_t rots,
+               size_t batch, uint32_t terms, uint32_t comps, const LtViewed *V) {
+  HoistArgs H;
+  if (const int st = apply_call(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &H))
+    return st;
+  if (!batch) return NTTMUL_OK;
+  LtDev &d = h->dev[0];
+  size_t words[5];
+  lintrans_words(h->plan.L, h->plan.K, h->plan.n, batch, terms, rots, comps, words);
+  if (V) {
+    words[2] = V->b_words;
+    words[3] = V->w_words;
+  }
+  const size_t wb = (size_t)h->plan.word_bits / 8;
+  // (a NULL w_hat or c0_hat: no bytes, no buffer, and the NULL reaches the launch)
+  const Staged ops[5] = {{nullptr, c_hat, words[0] * wb},
+                         {a_hat, nullptr, words[1] * wb},
+                         {b_hat, nullptr, words[2] * wb},
+                         {w_hat, nullptr, w_hat ? words[3] * wb : 0},
+                         {c0_hat, nullptr, c0_hat ? words[4] * wb : 0}};
+  DeviceGuard guard;
+  LIMB_TRY(h->err, hipSetDevice(d.base.id));
+  void *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int st = staged_begin(h->err, d.base, "lintrans", ops, 5, buf);
+  if (!st)
+    st = run(h, d, buf[0], buf[1], buf[2], buf[3], buf[4], H, batch, terms, d.base.stream, V);
+  return staged_end(h->err, d.base, "lintrans", ops, 5, buf, st);
+}
+
 }  // namespace
+
+namespace nttmul {
+
+int lintrans_apply_viewed(nttmul_lintrans *h, const LtViewed &V, void *c_hat, const void *a_hat,
+                          const void *b_hat, const void *w_hat, const void *c0_hat,
+                          const uint32_t *k, uint32_t rots, size_t batch, uint32_t terms,
+                          uint32_t comps, int host, int dev, void *stream) {
+  if (host)
+    return apply_host(h, c_hat, a_hat, b_hat, w_hat, c0_hat, k, rots, batch, terms, comps, &V);
+  return apply_device(h, c_hat, a_hat, b_hat, w_hat, c0_hat, k, rots, batch, terms, comps, dev,
+                      stream, &V);
+}
+
+}  // namespace nttmul
 
 extern "C" {
 
@@ -167,37 +234,14 @@ int nttmul_lintrans_apply_device(nttmul_lintrans *h, void *c_hat, const void *a_
                                  const void *b_hat, const void *w_hat, const void *c0_hat,
                                  const uint32_t *k, uint32_t rots, size_t batch, uint32_t terms,
                                  uint32_t comps, int dev, void *stream) {
-  HoistArgs H;
-  if (const int st = apply_call(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &H))
-    return st;
-  return on_device(h->err, h->dev, h->ndev, dev, [&](LtDev &d) {
-    return run(h, d, c_hat, a_hat, b_hat, w_hat, c0_hat, H, batch, terms, (hipStream_t)stream);
-  });
+  return apply_device(h, c_hat, a_hat, b_hat, w_hat, c0_hat, k, rots, batch, terms, comps, dev,
+                      stream, nullptr);
 }
 
 int nttmul_lintrans_apply(nttmul_lintrans *h, void *c_hat, const void *a_hat, const void *b_hat,
                           const void *w_hat, const void *c0_hat, const uint32_t *k, uint32_t rots,
                           size_t batch, uint32_t terms, uint32_t comps) {
-  HoistArgs H;
-  if (const int st = apply_call(h, c_hat, a_hat, b_hat, k, rots, batch, terms, comps, &H))
-    return st;
-  if (!batch) return NTTMUL_OK;
-  LtDev &d = h->dev[0];
-  size_t words[5];
-  lintrans_words(h->plan.L, h->plan.K, h->plan.n, batch, terms, rots, comps, words);
-  const size_t wb = (size_t)h->plan.word_bits / 8;
-  // (a NULL w_hat or c0_hat: no bytes, no buffer, and the NULL reaches the launch)
-  const Staged ops[5] = {{nullptr, c_hat, words[0] * wb},
-                         {a_hat, nullptr, words[1] * wb},
-                         {b_hat, nullptr, words[2] * wb},
-                         {w_hat, nullptr, w_hat ? words[3] * wb : 0},
-                         {c0_hat, nullptr, c0_hat ? words[4] * wb : 0}};
-  DeviceGuard guard;
-  LIMB_TRY(h->err, hipSetDevice(d.base.id));
-  void *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int st = staged_begin(h->err, d.base, "lintrans", ops, 5, buf);
-  if (!st) st = run(h, d, buf[0], buf[1], buf[2], buf[3], buf[4], H, batch, terms, d.base.stream);
-  return staged_end(h->err, d.base, "lintrans", ops, 5, buf, st);
+  return apply_host(h, c_hat, a_hat, b_hat, w_hat, c0_hat, k, rots, batch, terms, comps, nullptr);
 }
 
 int nttmul_lintrans_kernel_name(const nttmul_lintrans *h, uint32_t comps, int weighted, char *buf,

@@ -30,4 +30,23 @@ hipError_t launch_lintrans(const LtTables &T, void *c_hat, const void *a_hat, co
 // "k_lintrans<Arith64,u64,2,1>": the dry run of the launching statement itself
 hipError_t describe_lintrans(const LtTables &T, uint32_t comps, bool weighted, std::string *out);
 
+// apply with b_hat and, when given, w_hat viewed (ksntt.hpp KsnttViewed's shape): `check` in
+// place of their range checks, `launch` in place of launch_lintrans, b_words and w_words the whole
+// viewed operands (what the host form stages)
+struct LtViewed {
+  const LevelAddr *addr;
+  size_t b_words, w_words;
+  LevelCheck check;
+  hipError_t (*launch)(const LtTables &T, void *c_hat, const void *a_hat, const void *b_hat,
+                       const void *w_hat, const void *c0_hat, const HoistArgs &H, size_t batch,
+                       uint32_t terms, const LevelAddr &A, hipStream_t s);
+};
+// nttmul_lintrans_apply (host != 0; dev and stream unused) or nttmul_lintrans_apply_device with V
+// for b_hat and w_hat: the same argument checks, device selection, range checks of a_hat and
+// c0_hat and error text
+int lintrans_apply_viewed(nttmul_lintrans *h, const LtViewed &V, void *c_hat, const void *a_hat,
+                          const void *b_hat, const void *w_hat, const void *c0_hat,
+                          const uint32_t *k, uint32_t rots, size_t batch, uint32_t terms,
+                          uint32_t comps, int host, int dev, void *stream);
+
 }  // namespace nttmul

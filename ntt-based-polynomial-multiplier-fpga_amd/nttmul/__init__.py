@@ -1862,7 +1862,7 @@ class NttKeySwitch(_Handle):
         q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
         prm.ndev, prm.first_dev, prm.scratch_mb = ndev, first_dev, scratch_mb
         info = KsNttInfo()
-        self._open(load_ksntt_library(), info, prm, qa, len(q), pa, len(p), alpha)  # self.info
+        self._open(self._library(), info, prm, qa, len(q), pa, len(p), alpha)  # self.info
         self.n, self.word_bits = info.n, info.word_bits
         self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
         self.limbs = info.q_limbs + info.p_limbs
@@ -1870,6 +1870,11 @@ class NttKeySwitch(_Handle):
         self.scratch_mb = info.scratch_mb
         self.q, self.p = tuple(q), tuple(p)
         self.first_dev = first_dev
+
+    @staticmethod
+    def _library() -> ctypes.CDLL:
+        """The library the context is created through (a subclass: a library built on it)."""
+        return load_ksntt_library()
 
     def kernel_name(self, op, comps: int = 1) -> str:
         """nttmul_ksntt_kernel_name for op 0..1 or "modup" / "mac": a sub-batch's kernels joined
@@ -1988,13 +1993,18 @@ class NttLinTrans(_Handle):
         q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
         prm.ndev, prm.first_dev = ndev, first_dev
         info = LinTransInfo()
-        lib = load_lintrans_library(lib_path) if lib_path else load_lintrans_library()
+        lib = load_lintrans_library(lib_path) if lib_path else self._library()
         self._open(lib, info, prm, qa, len(q), pa, len(p))  # self.info
         self.n, self.word_bits = info.n, info.word_bits
         self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
         self.limbs = info.q_limbs + info.p_limbs
         self.q, self.p = tuple(q), tuple(p)
         self.first_dev = first_dev
+
+    @staticmethod
+    def _library() -> ctypes.CDLL:
+        """The library the context is created through (a subclass: a library built on it)."""
+        return load_lintrans_library()
 
     def kernel_name(self, comps: int = 1, weighted: bool = False) -> str:
         """nttmul_lintrans_kernel_name, e.g. "k_lintrans<Arith64,u64,2,1>"."""
@@ -2116,13 +2126,18 @@ class NttCtMul(_Handle):
         q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
         prm.ndev, prm.first_dev = ndev, first_dev
         info = CtMulInfo()
-        lib = load_ctmul_library(lib_path) if lib_path else load_ctmul_library()
+        lib = load_ctmul_library(lib_path) if lib_path else self._library()
         self._open(lib, info, prm, qa, len(q), pa, len(p))  # self.info
         self.n, self.word_bits = info.n, info.word_bits
         self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
         self.limbs = info.q_limbs + info.p_limbs
         self.q, self.p = tuple(q), tuple(p)
         self.first_dev = first_dev
+
+    @staticmethod
+    def _library() -> ctypes.CDLL:
+        """The library the context is created through (a subclass: a library built on it)."""
+        return load_ctmul_library()
 
     def kernel_name(self, op) -> str:
         """nttmul_ctmul_kernel_name for op 0..1 or "high" / "relin", e.g.
@@ -2353,6 +2368,239 @@ class NttExactConv(_Handle):
     def moddown(self, x_hat) -> np.ndarray:
         """x_hat of shape [batch, L + K, n]; returns [batch, L, n]."""
         return self._host("moddown", x_hat)
+
+
+# ---- level views of the key operands (include/nttmul_level.h) ------------------------------------
+
+LEVEL_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_level.so")
+LEVEL_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_level.h")
+LEVEL_OPS = ("mac", "lintrans", "relin")
+
+
+class LevelView(ctypes.Structure):
+    """nttmul_level_view: the limbs of Q and the terms the viewed operand was made with."""
+    _fields_ = [("top_q_limbs", ctypes.c_uint32), ("top_terms", ctypes.c_uint32)]
+
+
+def load_level_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_level.so (include/nttmul_level.h): the ABI and kernels of
+    libnttmul_xconv.so plus the view forms of mac, apply and relin.  The other loaders are
+    unaffected."""
+    return _load_limb_library(LEVEL_LIB_PATH, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn,
+                              _bind_hoist, _bind_mdntt, _bind_ksntt, _bind_lintrans, _bind_ctmul,
+                              _bind_xconv, _bind_level)
+
+
+def _bind_level(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u32p, view = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(LevelView)
+    lib.nttmul_ksntt_mac_view_device.argtypes = [vp, vp, vp, vp, u32p, u32, sz, u32, u32, view,
+                                                 i32, vp]
+    lib.nttmul_ksntt_mac_view.argtypes = [vp, vp, vp, vp, u32p, u32, sz, u32, u32, view]
+    lib.nttmul_lintrans_apply_view_device.argtypes = [vp, vp, vp, vp, vp, vp, u32p, u32, sz, u32,
+                                                      u32, view, i32, vp]
+    lib.nttmul_lintrans_apply_view.argtypes = [vp, vp, vp, vp, vp, vp, u32p, u32, sz, u32, u32,
+                                               view]
+    lib.nttmul_ctmul_relin_view_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, u32, u32, view,
+                                                   i32, vp]
+    lib.nttmul_ctmul_relin_view.argtypes = [vp, vp, vp, vp, vp, vp, sz, u32, u32, view]
+    lib.nttmul_level_kernel_name.argtypes = [i32, u32, u32, u32, i32, ctypes.c_char_p, sz]
+
+
+def level_exported_symbols() -> list:
+    """Function names declared in include/nttmul_level.h."""
+    return _header_symbols(LEVEL_HEADER_PATH, "nttmul_")
+
+
+def level_kernel_name(op, logn: int, word_bits: int, comps: int = 1,
+                      weighted: bool = False) -> str:
+    """nttmul_level_kernel_name for op 0..2 or "mac" / "lintrans" / "relin", e.g.
+    "k_level_lintrans<Arith64,u64,2,1>".  Needs no context and no device."""
+    lib = load_level_library()
+    op = LEVEL_OPS.index(op) if isinstance(op, str) else int(op)
+    buf = ctypes.create_string_buffer(256)
+    st = lib.nttmul_level_kernel_name(op, logn, word_bits, comps, int(bool(weighted)), buf,
+                                      len(buf))
+    if st < 0:
+        raise NttmulError(st, lib.nttmul_strerror(st).decode())
+    return buf.value.decode()
+
+
+def _level_view(view) -> LevelView:
+    top_q_limbs, top_terms = view
+    return LevelView(int(top_q_limbs), int(top_terms))
+
+
+def _viewed_host(x, dtype, ndim: int, tail: tuple, what: str) -> np.ndarray:
+    x = np.ascontiguousarray(x, dtype=dtype)
+    if x.ndim != ndim or x.shape[-len(tail):] != tail:
+        raise ValueError(f"{what} must have shape [..., {', '.join(map(str, tail))}]")
+    return x
+
+
+class NttLevelKeySwitch(NttKeySwitch):
+    """An NttKeySwitch created through lib/libnttmul_level.so: every NttKeySwitch method, and
+    mac / mac_device take view=(top_q_limbs, top_terms) (include/nttmul_level.h): b_hat is then
+    the key made for the chain's top level, [rots][comps][top_terms][top_q_limbs + K][n], and the
+    context, whose q must be the first L primes of that chain, reads its own limbs and terms of
+    it.  view=None is the dense call."""
+
+    @staticmethod
+    def _library() -> ctypes.CDLL:
+        return load_level_library()
+
+    def mac_device(self, c_hat, a_hat, b_hat, ks, batch: int, terms: int, comps: int,
+                   dev: Optional[int] = None, stream: int = 0, view=None):
+        if view is None:
+            return super().mac_device(c_hat, a_hat, b_hat, ks, batch, terms, comps, dev, stream)
+        dev = self.first_dev if dev is None else dev
+        v = _level_view(view)
+        ks = [int(k) for k in ks]
+        rots = len(ks)
+        args = [_dev_arg(t, k, self.n, self.word_bits, dev)
+                for t, k in zip((c_hat, a_hat, b_hat),
+                                (batch * rots * comps * self.limbs, batch * terms * self.limbs,
+                                 rots * comps * v.top_terms * (v.top_q_limbs + self.p_limbs)))]
+        karr = (ctypes.c_uint32 * max(1, rots))(*ks)
+        self._check(self._c.mac_view_device(self._h, *args, karr, rots, batch, terms, comps,
+                                            ctypes.byref(v), dev, stream or None))
+
+    def mac(self, a_hat, b_hat, ks, view=None) -> np.ndarray:
+        """view given: b_hat of shape [rots, comps, top_terms, top_q_limbs + K, n]; the call's
+        terms are a_hat's."""
+        if view is None:
+            return super().mac(a_hat, b_hat, ks)
+        v = _level_view(view)
+        a_hat = np.ascontiguousarray(a_hat, dtype=self.io_dtype)
+        ks = [int(k) for k in ks]
+        if a_hat.ndim != 4 or a_hat.shape[2:] != (self.limbs, self.n) or a_hat.shape[1] == 0:
+            raise ValueError(f"mac: a_hat must have shape [batch, terms > 0, {self.limbs}, {self.n}]")
+        b_hat = _viewed_host(b_hat, self.io_dtype, 5,
+                             (v.top_terms, v.top_q_limbs + self.p_limbs, self.n), "mac: b_hat")
+        if b_hat.shape[0] != len(ks):
+            raise ValueError("mac: b_hat must have len(ks) rotations")
+        rots, comps = b_hat.shape[:2]
+        c = np.empty((a_hat.shape[0], rots, comps, self.limbs, self.n), dtype=self.io_dtype)
+        karr = (ctypes.c_uint32 * max(1, rots))(*ks)
+        self._check(self._c.mac_view(self._h, c.ctypes.data, a_hat.ctypes.data, b_hat.ctypes.data,
+                                     karr, rots, a_hat.shape[0], a_hat.shape[1], comps,
+                                     ctypes.byref(v)))
+        return c
+
+
+class NttLevelLinTrans(NttLinTrans):
+    """An NttLinTrans created through lib/libnttmul_level.so: every NttLinTrans method, and
+    apply / apply_device take view=(top_q_limbs, top_terms): b_hat is then
+    [rots][comps][top_terms][top_q_limbs + K][n] and w_hat, when given,
+    [rots][top_q_limbs + K][n], both made for the chain's top level.  view=None is the dense
+    call."""
+
+    @staticmethod
+    def _library() -> ctypes.CDLL:
+        return load_level_library()
+
+    def apply_device(self, c_hat, a_hat, b_hat, k, batch: int, terms: int, comps: int,
+                     w_hat=None, c0_hat=None, dev: Optional[int] = None, stream: int = 0,
+                     view=None):
+        if view is None:
+            return super().apply_device(c_hat, a_hat, b_hat, k, batch, terms, comps, w_hat,
+                                        c0_hat, dev, stream)
+        dev = self.first_dev if dev is None else dev
+        v = _level_view(view)
+        k = [int(x) for x in k]
+        rots = len(k)
+        top = v.top_q_limbs + self.p_limbs
+        args = [_dev_arg(t, m, self.n, self.word_bits, dev)
+                for t, m in zip((c_hat, a_hat, b_hat),
+                                (batch * comps * self.limbs, batch * terms * self.limbs,
+                                 rots * comps * v.top_terms * top))]
+        wp = None if w_hat is None else _dev_arg(w_hat, rots * top, self.n, self.word_bits, dev)
+        zp = None if c0_hat is None else _dev_arg(c0_hat, batch * self.q_limbs, self.n,
+                                                  self.word_bits, dev)
+        karr = (ctypes.c_uint32 * max(1, rots))(*k)
+        self._check(self._c.apply_view_device(self._h, *args, wp, zp, karr, rots, batch, terms,
+                                              comps, ctypes.byref(v), dev, stream or None))
+
+    def apply(self, a_hat, b_hat, k, w_hat=None, c0_hat=None, view=None) -> np.ndarray:
+        """view given: b_hat of shape [rots, comps, top_terms, top_q_limbs + K, n] and w_hat of
+        shape [rots, top_q_limbs + K, n] or None; the call's terms are a_hat's."""
+        if view is None:
+            return super().apply(a_hat, b_hat, k, w_hat, c0_hat)
+        v = _level_view(view)
+        top = v.top_q_limbs + self.p_limbs
+        a_hat = np.ascontiguousarray(a_hat, dtype=self.io_dtype)
+        k = [int(x) for x in k]
+        if a_hat.ndim != 4 or a_hat.shape[2:] != (self.limbs, self.n) or a_hat.shape[1] == 0:
+            raise ValueError(f"apply: a_hat must have shape [batch, terms > 0, {self.limbs}, {self.n}]")
+        b_hat = _viewed_host(b_hat, self.io_dtype, 5, (v.top_terms, top, self.n), "apply: b_hat")
+        if b_hat.shape[0] != len(k):
+            raise ValueError("apply: b_hat must have len(k) rotations")
+        rots, comps = b_hat.shape[:2]
+        batch = a_hat.shape[0]
+        wp = zp = None
+        if w_hat is not None:
+            w_hat = _viewed_host(w_hat, self.io_dtype, 3, (rots, top, self.n), "apply: w_hat")
+            wp = w_hat.ctypes.data
+        if c0_hat is not None:
+            c0_hat = np.ascontiguousarray(c0_hat, dtype=self.io_dtype)
+            if c0_hat.shape != (batch, self.q_limbs, self.n):
+                raise ValueError("apply: c0_hat must have shape [batch, L, n]")
+            zp = c0_hat.ctypes.data
+        c = np.empty((batch, comps, self.limbs, self.n), dtype=self.io_dtype)
+        karr = (ctypes.c_uint32 * max(1, rots))(*k)
+        self._check(self._c.apply_view(self._h, c.ctypes.data, a_hat.ctypes.data,
+                                       b_hat.ctypes.data, wp, zp, karr, rots, batch,
+                                       a_hat.shape[1], comps, ctypes.byref(v)))
+        return c
+
+
+class NttLevelCtMul(NttCtMul):
+    """An NttCtMul created through lib/libnttmul_level.so: every NttCtMul method, and
+    relin / relin_device take view=(top_q_limbs, top_terms): key_hat is then
+    [2][top_terms][top_q_limbs + K][n], the relinearisation key made for the chain's top level.
+    view=None is the dense call."""
+
+    @staticmethod
+    def _library() -> ctypes.CDLL:
+        return load_level_library()
+
+    def relin_device(self, c_hat, up_hat, key_hat, x_hat, y_hat, batch: int, pairs: int,
+                     terms: int, dev: Optional[int] = None, stream: int = 0, view=None):
+        if view is None:
+            return super().relin_device(c_hat, up_hat, key_hat, x_hat, y_hat, batch, pairs, terms,
+                                        dev, stream)
+        dev = self.first_dev if dev is None else dev
+        v = _level_view(view)
+        args = [_dev_arg(t, m, self.n, self.word_bits, dev)
+                for t, m in zip((c_hat, up_hat, key_hat),
+                                (batch * 2 * self.limbs, batch * terms * self.limbs,
+                                 2 * v.top_terms * (v.top_q_limbs + self.p_limbs)))]
+        xp, yp = self._pair_args(x_hat, y_hat, batch, pairs, dev)
+        self._check(self._c.relin_view_device(self._h, *args, xp, yp, batch, pairs, terms,
+                                              ctypes.byref(v), dev, stream or None))
+
+    def relin(self, up_hat, key_hat, x_hat, y_hat, view=None) -> np.ndarray:
+        """view given: key_hat of shape [2, top_terms, top_q_limbs + K, n]; the call's terms are
+        up_hat's."""
+        if view is None:
+            return super().relin(up_hat, key_hat, x_hat, y_hat)
+        v = _level_view(view)
+        up_hat = np.ascontiguousarray(up_hat, dtype=self.io_dtype)
+        x_hat, y_hat = self._host_pairs("relin", x_hat, y_hat)
+        if up_hat.ndim != 4 or up_hat.shape[2:] != (self.limbs, self.n) or up_hat.shape[1] == 0:
+            raise ValueError(f"relin: up_hat must have shape [batch, terms > 0, {self.limbs}, "
+                             f"{self.n}]")
+        key_hat = _viewed_host(key_hat, self.io_dtype, 4,
+                               (2, v.top_terms, v.top_q_limbs + self.p_limbs, self.n),
+                               "relin: key_hat")
+        if x_hat.shape[0] != up_hat.shape[0]:
+            raise ValueError("relin: x_hat and up_hat must have the same batch")
+        batch, pairs = x_hat.shape[:2]
+        c = np.empty((batch, 2, self.limbs, self.n), dtype=self.io_dtype)
+        self._check(self._c.relin_view(self._h, c.ctypes.data, up_hat.ctypes.data,
+                                       key_hat.ctypes.data, x_hat.ctypes.data, y_hat.ctypes.data,
+                                       batch, pairs, up_hat.shape[1], ctypes.byref(v)))
+        return c
 
 
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
