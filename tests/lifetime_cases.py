@@ -276,8 +276,9 @@ SERVER_SEQUENCES = {"S1": SEQ_S1, "S2": SEQ_S2, "S2_512": SEQ_S2_512, "S2_1024":
                     "S6_cool": SEQ_S6_COOL, "S6_off": SEQ_S6_OFF, "S6_fresh": SEQ_S6_FRESH}
 ALL_SEQUENCES = {**SEQUENCES, **SERVER_SEQUENCES}
 
-# I. one caller stream through the four libraries (no per-context state to model: the stages are
-# listed in tests/test_gpu_lifetime.py); n, batch, terms
+# I. one caller stream through the four libraries (the stages are listed in
+# tests/test_gpu_lifetime.py; the scratch state the limb-aware libraries keep per context is
+# modelled in tests/limb_lifetime_cases.py); n, batch, terms
 CHAIN = (1024, 3, 2)
 # J. two host threads, a context each: the pairs of sequences that run together
 THREAD_PAIRS = (("A", "C"), ("A", "B"))
