@@ -83,8 +83,10 @@
  * Out of scope here:
  *   - high fused into the loads of nttmul_ksntt_modup's inverse kernels;
  *   - a key, or a plaintext operand, per batch entry;
- *   - ciphertext x plaintext (a per-limb pointwise product, no key);
- *   - three-component ciphertexts as inputs;
+ *   - ciphertext x plaintext, ciphertext sums and constants (no key): nttmul_ctlin.h,
+ *     lib/libnttmul_ctlin.so, nttmul_ctlin_combine;
+ *   - three-component ciphertexts: their sums are nttmul_ctlin.h's combine with comps = 3 and
+ *     all three terms of a product its tensor; as inputs of a product they stay out of scope;
  *   - rounding in ModDown, and exact conversion (the alpha correction): both are nttmul_xconv.h,
  *     lib/libnttmul_xconv.so, whose moddown reads what this header's calls write;
  *   - cyclic contexts (NTTMUL_FLAG_CYCLIC), the class 2^31 <= q < 2^32;

@@ -2603,6 +2603,203 @@ class NttLevelCtMul(NttCtMul):
         return c
 
 
+# ---- ciphertext sums, plaintext products, the full tensor (include/nttmul_ctlin.h) ---------------
+
+CTLIN_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_ctlin.so")
+CTLIN_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_ctlin.h")
+CTLIN_OPS = ("combine", "tensor")
+CTLIN_MAX_TERMS, CTLIN_MAX_COMPS = 16, 3
+CTLIN_ONE, CTLIN_SCALAR, CTLIN_PLAIN = 0, 1, 2
+
+
+class CtLinInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("limbs", ctypes.c_uint32),
+                ("word_bits", ctypes.c_uint32), ("ndev", ctypes.c_int)]
+
+
+class CtLinTerm(ctypes.Structure):
+    """nttmul_ctlin_term."""
+    _fields_ = [("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("kind", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def load_ctlin_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_ctlin.so (include/nttmul_ctlin.h): the ABI and kernels of
+    libnttmul_level.so plus combine and tensor.  The other loaders are unaffected."""
+    return _load_limb_library(CTLIN_LIB_PATH, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn,
+                              _bind_hoist, _bind_mdntt, _bind_ksntt, _bind_lintrans, _bind_ctmul,
+                              _bind_xconv, _bind_level, _bind_ctlin)
+
+
+def _bind_ctlin(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    terms = ctypes.POINTER(CtLinTerm)
+    _bind_handle(lib, "nttmul_ctlin", CtLinInfo, [ctypes.POINTER(ctypes.c_uint64), u32])
+    lib.nttmul_ctlin_combine_device.argtypes = [vp, vp, terms, u32, sz, u32, i32, vp]
+    lib.nttmul_ctlin_combine.argtypes = [vp, vp, terms, u32, sz, u32]
+    lib.nttmul_ctlin_tensor_device.argtypes = [vp, vp, vp, vp, sz, u32, i32, vp]
+    lib.nttmul_ctlin_tensor.argtypes = [vp, vp, vp, vp, sz, u32]
+    lib.nttmul_ctlin_kernel_name.argtypes = [vp, i32, u32, ctypes.c_char_p, sz]
+
+
+def ctlin_exported_symbols() -> list:
+    """Function names declared in include/nttmul_ctlin.h."""
+    return _header_symbols(CTLIN_HEADER_PATH, "nttmul_ctlin_")
+
+
+def ctlin_one(x) -> tuple:
+    """The term x (weight 1) of NttCtLin.combine: (x, w, kind)."""
+    return (x, None, CTLIN_ONE)
+
+
+def ctlin_scalar(x, w) -> tuple:
+    """The term w[l] x: w holds one constant per limb, [L]."""
+    return (x, w, CTLIN_SCALAR)
+
+
+def ctlin_plain(x, w) -> tuple:
+    """The term w o x: w is an NTT-domain plaintext [L, n], shared by batch and components."""
+    return (x, w, CTLIN_PLAIN)
+
+
+def ctlin_const_scalar(w) -> tuple:
+    """The constant w[l] added to component 0 (every slot)."""
+    return (None, w, CTLIN_SCALAR)
+
+
+def ctlin_const_plain(w) -> tuple:
+    """The NTT-domain plaintext w [L, n] added to component 0."""
+    return (None, w, CTLIN_PLAIN)
+
+
+class NttCtLin(_Handle):
+    """nttmul_ctlin: one basis q of L primes of one word class for one degree n in 256 .. 65536
+    (include/nttmul_ctlin.h).  Every limb of every operand is in NTT order, as RnsContext /
+    RnsMpContext.forward writes it.
+
+    combine is out[p][c] = sum_i W_i o X_i[p][c] over terms made by ctlin_one, ctlin_scalar,
+    ctlin_plain, ctlin_const_scalar and ctlin_const_plain, every x and out [batch, comps, L, n]
+    with comps in 1 .. 3.  tensor is (d_0, d_1, d_2) [batch, 3, L, n] of x_hat, y_hat
+    [batch, pairs, 2, L, n]; the same array for both is the square.
+
+    Caller memory: operands need the alignment of their word only; combine's out may be exactly
+    one or more of its x (the same array) and must overlap nothing else, tensor's output must
+    overlap no input; combine writes exactly batch * comps * L * n words, tensor batch * 3 * L * n,
+    and neither writes an input."""
+
+    _PREFIX = "nttmul_ctlin"
+    _OPS = CTLIN_OPS
+
+    def __init__(self, n: int, q, ndev: int = 1, first_dev: int = 0, validate: bool = False,
+                 cyclic: bool = False, share_devices: bool = False):
+        q = [int(m) for m in q]
+        prm = _Params(n, 0, 0, ndev, first_dev, _flags(validate, cyclic, share_devices), 0, 0, 0,
+                      0, 0)
+        qa = (ctypes.c_uint64 * max(1, len(q)))(*q)
+        info = CtLinInfo()
+        self._open(load_ctlin_library(), info, prm, qa, len(q))   # self.info
+        self.n, self.limbs, self.word_bits = info.n, info.limbs, info.word_bits
+        self.q = tuple(q)
+        self.first_dev = first_dev
+
+    def kernel_name(self, op, comps: int = 1) -> str:
+        """nttmul_ctlin_kernel_name for op 0..1 or "combine" / "tensor", e.g.
+        "k_ctlin_combine<Arith64,u64,2>" (comps is ignored by tensor)."""
+        return self._kernel_name(op, comps)
+
+    def _terms(self, terms, ptr_of):
+        """The nttmul_ctlin_term array of [(x, w, kind), ..]; ptr_of(operand, polys, words)."""
+        terms = list(terms)
+        arr = (CtLinTerm * max(1, len(terms)))()
+        for t, (x, w, kind) in zip(arr, terms):
+            t.kind, t.reserved = int(kind), 0
+            t.x = None if x is None else ptr_of(x, None)
+            t.w = None if w is None else ptr_of(w, kind)
+        return arr, len(terms)
+
+    def combine_device(self, out, terms, batch: int, comps: int, dev: Optional[int] = None,
+                       stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        every x [batch][comps][L][n], a scalar's w [L], a plaintext's w [L][n] ->
+        out [batch][comps][L][n].  out may be one or more of the x."""
+        dev = self.first_dev if dev is None else dev
+        polys = batch * comps * self.limbs
+
+        def ptr_of(v, kind):
+            if kind is None:
+                return _dev_arg(v, polys, self.n, self.word_bits, dev)
+            if kind == CTLIN_SCALAR:
+                return _dev_arg(v, self.limbs, 1, self.word_bits, dev)
+            return _dev_arg(v, self.limbs, self.n, self.word_bits, dev)
+
+        op = _dev_arg(out, polys, self.n, self.word_bits, dev)
+        arr, count = self._terms(terms, ptr_of)
+        self._check(self._c.combine_device(self._h, op, arr, count, batch, comps, dev,
+                                           stream or None))
+
+    def combine(self, terms, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """terms of numpy arrays: every x of one shape [batch, comps, L, n], a scalar's w [L], a
+        plaintext's w [L, n]; a call of constant terms alone needs `out` for its shape.  out: the
+        array written and returned (it may be one or more of the x); a new one by default."""
+        terms = list(terms)
+        dt = self.io_dtype
+        keep, shape = [], None if out is None else out.shape
+
+        def host(v, kind):
+            if v is out:
+                return out.ctypes.data
+            a = np.ascontiguousarray(v, dtype=dt)
+            keep.append(a)
+            return a.ctypes.data
+
+        for x, w, kind in terms:
+            if x is not None:
+                if shape is None:
+                    shape = np.shape(x)
+                if np.shape(x) != shape:
+                    raise ValueError("combine: every x must have out's shape")
+            if w is not None and np.shape(w) != ((self.limbs,) if kind == CTLIN_SCALAR
+                                                 else (self.limbs, self.n)):
+                raise ValueError("combine: w must have shape [L] (scalar) or [L, n] (plaintext)")
+        if shape is None or len(shape) != 4 or shape[2:] != (self.limbs, self.n):
+            raise ValueError(f"combine: x must have shape [batch, comps, {self.limbs}, {self.n}]")
+        if out is None:
+            out = np.empty(shape, dtype=dt)
+        elif not (isinstance(out, np.ndarray) and out.dtype == dt and out.flags.c_contiguous):
+            raise ValueError("combine: out must be a contiguous array of the context's words")
+        arr, count = self._terms(terms, host)
+        self._check(self._c.combine(self._h, out.ctypes.data, arr, count, shape[0], shape[1]))
+        return out
+
+    def tensor_device(self, d_hat, x_hat, y_hat, batch: int, pairs: int,
+                      dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        x_hat, y_hat [batch][pairs][2][L][n] -> d_hat [batch][3][L][n]."""
+        dev = self.first_dev if dev is None else dev
+        out = _dev_arg(d_hat, batch * 3 * self.limbs, self.n, self.word_bits, dev)
+        polys = batch * pairs * 2 * self.limbs
+        xp = _dev_arg(x_hat, polys, self.n, self.word_bits, dev)
+        yp = xp if y_hat is x_hat else _dev_arg(y_hat, polys, self.n, self.word_bits, dev)
+        self._check(self._c.tensor_device(self._h, out, xp, yp, batch, pairs, dev, stream or None))
+
+    def tensor(self, x_hat, y_hat) -> np.ndarray:
+        """x_hat, y_hat of shape [batch, pairs, 2, L, n] (the same array: the square).  Returns
+        d_hat of shape [batch, 3, L, n]."""
+        same = y_hat is x_hat
+        x_hat = np.ascontiguousarray(x_hat, dtype=self.io_dtype)
+        y_hat = x_hat if same else np.ascontiguousarray(y_hat, dtype=self.io_dtype)
+        if x_hat.ndim != 5 or x_hat.shape[2:] != (2, self.limbs, self.n) or x_hat.shape[1] == 0:
+            raise ValueError(f"tensor: x_hat must have shape [batch, pairs > 0, 2, {self.limbs}, "
+                             f"{self.n}]")
+        if y_hat.shape != x_hat.shape:
+            raise ValueError("tensor: y_hat must have x_hat's shape")
+        batch, pairs = x_hat.shape[:2]
+        d = np.empty((batch, 3, self.limbs, self.n), dtype=self.io_dtype)
+        self._check(self._c.tensor(self._h, d.ctypes.data, x_hat.ctypes.data, y_hat.ctypes.data,
+                                   batch, pairs))
+        return d
+
+
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
 
 class _HostBlock:
