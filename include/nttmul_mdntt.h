@@ -27,8 +27,11 @@
  * integer.  Only the K special limbs are transformed back: L + K transforms instead of 2L + K,
  * and two launches (n <= 4096) or four (n > 4096) instead of three or five.
  *
- * K = 1 with P = {the last prime} is the CKKS / BGV rescale from level L + 1 to level L, and it
- * is exact: out = NTT(floor(X / p) mod q_l) for the CRT value X of the input over Q u {p}.
+ * K = 1 with P = {the last prime} is the CKKS rescale from level L + 1 to level L in its floor
+ * form, and it is exact: out = NTT(floor(X / p) mod q_l) for the CRT value X of the input over
+ * Q u {p}.  It is not BGV's: the subtrahend [X]_p is not 0 modulo the plaintext modulus, so the
+ * message in the low bits does not survive it (nttmul_tmd.h, lib/libnttmul_tmd.so, has BGV's
+ * ModDown and rescale on the same operands).
  *
  * Word size, as nttmul_rns.h: every modulus of both bases below 2^31 (32-bit words) or every one
  * in [2^32, 2^62) (64-bit words); nttmul_mdntt_info.word_bits says which.

@@ -72,7 +72,8 @@
  * the streams passed to the *_device calls: synchronise them first.
  *
  * Out of scope here:
- *   - BGV's t-correcting ModDown;
+ *   - BGV's t-correcting ModDown (nttmul_tmd.h, lib/libnttmul_tmd.so, has it on the same operands,
+ *     built on the uncorrected sum S instead of the centred c);
  *   - a computed once per coefficient in a pass of its own (each of the L target-limb workgroups
  *     recomputes it; tools/bench_xconv.py measures what that costs);
  *   - a coefficient-order input or output;

@@ -1747,7 +1747,7 @@ class NttModDown(_Handle):
     [batch, L + K, n], every limb in NTT order as RnsContext / RnsMpContext.forward writes it, to
     [batch, L, n] in NTT order: forward over q of KeySwitchBasis.moddown of inverse over q + p of
     x_hat, bit for bit, with only the K limbs of p transformed back.  p = (the last prime,) is the
-    CKKS / BGV rescale.
+    CKKS rescale in its floor form (BGV's is NttPlainModDown).
 
     Caller memory: operands need the alignment of their word only; out must not overlap x_hat;
     a call writes exactly batch * L * n words of out and never writes x_hat.
@@ -2798,6 +2798,129 @@ class NttCtLin(_Handle):
         self._check(self._c.tensor(self._h, d.ctypes.data, x_hat.ctypes.data, y_hat.ctypes.data,
                                    batch, pairs))
         return d
+
+
+# ---- BGV's plaintext-preserving ModDown and rescale (include/nttmul_tmd.h) ------------------------
+
+TMD_LIB_PATH = os.path.join(PKG_DIR, "lib", "libnttmul_tmd.so")
+TMD_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "nttmul_tmd.h")
+
+
+class TmdInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("logn", ctypes.c_uint32), ("q_limbs", ctypes.c_uint32),
+                ("p_limbs", ctypes.c_uint32), ("word_bits", ctypes.c_uint32),
+                ("ndev", ctypes.c_int), ("scratch_mb", ctypes.c_uint32),
+                ("t", ctypes.c_uint64), ("msg_factor", ctypes.c_uint64)]
+
+
+def load_tmd_library() -> ctypes.CDLL:
+    """Load lib/libnttmul_tmd.so (include/nttmul_tmd.h): the ABI and kernels of
+    libnttmul_ctlin.so plus the plaintext-preserving ModDown.  The other loaders are
+    unaffected."""
+    return _load_limb_library(TMD_LIB_PATH, _bind_rns, _bind_rnsmp, _bind_ks, _bind_macn,
+                              _bind_hoist, _bind_mdntt, _bind_ksntt, _bind_lintrans, _bind_ctmul,
+                              _bind_xconv, _bind_level, _bind_ctlin, _bind_tmd)
+
+
+def _bind_tmd(lib: ctypes.CDLL) -> None:
+    vp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    u64, u64p = ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
+    _bind_handle(lib, "nttmul_tmd", TmdInfo, [u64p, u32, u64p, u32, u64])
+    lib.nttmul_tmd_moddown_device.argtypes = [vp, vp, vp, sz, i32, vp]
+    lib.nttmul_tmd_moddown.argtypes = [vp, vp, vp, sz]
+    lib.nttmul_tmd_plan.argtypes = [ctypes.POINTER(_Params), sz, u64p, u32, u64p, u32, u64,
+                                    vp, vp, vp, vp, vp]
+    lib.nttmul_tmd_kernel_name.argtypes = [vp, ctypes.c_char_p, sz]
+
+
+def tmd_exported_symbols() -> list:
+    """Function names declared in include/nttmul_tmd.h."""
+    return _header_symbols(TMD_HEADER_PATH, "nttmul_tmd_")
+
+
+def tmd_plan(q, p, t: int, n: int = 256, flags: int = 0):
+    """nttmul_tmd_plan, without a device: (yscale, g, w, v, msg_factor) in Python integers.
+    yscale[j] = Ph_j^-1 mod p_j; g[j] = -p_j^-1 mod t; w[j][l] = Ph_j mod q_l for j < K,
+    w[K][l] = P mod q_l and w[K + 1][l] = -P mod q_l; v[l] = P^-1 mod q_l; msg_factor = P^-1 mod
+    t.  The constants do not depend on n, which only has to suit the primes.  Raises NttmulError
+    with the status nttmul_tmd_create would return for these arguments before any device
+    access."""
+    lib = load_tmd_library()
+    q, p, prm, qa, pa = _ks_bases(n, q, p, flags)
+    L, K = len(q), len(p)
+    if not 0 <= t < 1 << 64:
+        raise NttmulError(NTTMUL_EINVAL, lib.nttmul_strerror(NTTMUL_EINVAL).decode())
+    sizes = (K, K, (K + 2) * L, L, 1)
+    tab = [(ctypes.c_uint64 * max(1, k))() for k in sizes]
+    st = lib.nttmul_tmd_plan(ctypes.byref(prm), ctypes.sizeof(prm), qa, L, pa, K, t,
+                             *(ctypes.addressof(x) for x in tab))
+    if st != NTTMUL_OK:
+        raise NttmulError(st, lib.nttmul_strerror(st).decode())
+    yscale, g, w, v, mf = (list(x[:k]) for x, k in zip(tab, sizes))
+    return yscale, g, [w[i:i + L] for i in range(0, len(w), L)], v, mf[0]
+
+
+class NttPlainModDown(_Handle):
+    """nttmul_tmd: the bases Q = q (L primes) and P = p (K primes), disjoint and of one word
+    class, and an odd plaintext modulus t >= 3, for one degree n in 256 .. 65536
+    (include/nttmul_tmd.h).  moddown maps x_hat [batch, L + K, n], every limb in NTT order as
+    RnsContext / RnsMpContext.forward writes it, to [batch, L, n] in NTT order: (X - d) / P mod q_l
+    for the CRT value X over Q u P, with d = X (mod P) and d = 0 (mod t), so that
+    P * out = X (mod t).  The message of a BGV ciphertext comes out multiplied by
+    self.msg_factor = P^-1 mod t.  p = (the last prime,) is the BGV rescale.  The result equals
+    NttModDown.moddown(x_hat) - forward(u), |u| <= (t - 1) / 2, bit for bit.
+
+    Caller memory: operands need the alignment of their word only; out must not overlap x_hat;
+    a call writes exactly batch * L * n words of out and never writes x_hat.
+
+    close() waits for the last use of the context's scratch, not for the streams passed to
+    moddown_device: synchronise them first."""
+
+    _PREFIX = "nttmul_tmd"
+    _NAME_CAP = 256
+
+    def __init__(self, n: int, q, p, t: int, ndev: int = 1, first_dev: int = 0,
+                 validate: bool = False, cyclic: bool = False, share_devices: bool = False,
+                 scratch_mb: int = 0):
+        q, p, prm, qa, pa = _ks_bases(n, q, p, _flags(validate, cyclic, share_devices))
+        prm.ndev, prm.first_dev, prm.scratch_mb = ndev, first_dev, scratch_mb
+        info = TmdInfo()
+        lib = load_tmd_library()
+        if not 0 <= t < 1 << 64:
+            raise NttmulError(NTTMUL_EINVAL, lib.nttmul_strerror(NTTMUL_EINVAL).decode())
+        self._open(lib, info, prm, qa, len(q), pa, len(p), t)
+        self.n, self.word_bits = info.n, info.word_bits
+        self.q_limbs, self.p_limbs = info.q_limbs, info.p_limbs
+        self.q, self.p, self.t = tuple(q), tuple(p), info.t
+        self.msg_factor = info.msg_factor
+        self.first_dev = first_dev
+
+    def kernel_name(self) -> str:
+        """nttmul_tmd_kernel_name: a sub-batch's kernels joined by " + ", e.g.
+        "k_mdntt_inv<Arith32P,u32,12> + k_tmd_fwd<Arith32P,u32,12>"."""
+        buf = ctypes.create_string_buffer(self._NAME_CAP)
+        st = self._c.kernel_name(self._h, buf, len(buf))
+        if st < 0:
+            self._check(st)
+        return buf.value.decode()
+
+    def moddown_device(self, out, x_hat, batch: int, dev: Optional[int] = None, stream: int = 0):
+        """Device-resident operands (pointers or torch tensors on `dev`), enqueued on `stream`:
+        x_hat [batch][L + K][n] -> out [batch][L][n]."""
+        dev = self.first_dev if dev is None else dev
+        args = [_dev_arg(x, batch * k, self.n, self.word_bits, dev)
+                for x, k in zip((out, x_hat), (self.q_limbs, self.q_limbs + self.p_limbs))]
+        self._check(self._c.moddown_device(self._h, *args, batch, dev, stream or None))
+
+    def moddown(self, x_hat) -> np.ndarray:
+        """x_hat of shape [batch, L + K, n]; returns [batch, L, n]."""
+        ext = self.q_limbs + self.p_limbs
+        x_hat = np.ascontiguousarray(x_hat, dtype=self.io_dtype)
+        if x_hat.ndim != 3 or x_hat.shape[1:] != (ext, self.n):
+            raise ValueError(f"moddown: x_hat must have shape [batch, {ext}, {self.n}]")
+        out = np.empty((x_hat.shape[0], self.q_limbs, self.n), dtype=self.io_dtype)
+        self._check(self._c.moddown(self._h, out.ctypes.data, x_hat.ctypes.data, x_hat.shape[0]))
+        return out
 
 
 # ---- planner API (SURVEY §8f row 2) ------------------------------------------------------------
