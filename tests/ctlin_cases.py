@@ -20,7 +20,6 @@ import basis_cases as BC
 OPS = ("combine", "tensor")
 ALL_N = tuple(1 << e for e in range(8, 17))
 PARITY_N = (256, 512, 4096, 8192)
-REF_MAX_N = 512                              # cases held to Python integers; above: the composition
 L = 3
 PROFILE = {32: "chain32", 64: "chain64"}
 MAX_TERMS, MAX_COMPS = 16, 3
@@ -181,7 +180,9 @@ def scale_cases():
     return out
 
 
-def all_cases():
+def referenced_cases():
+    """The cases whose every output word a GPU test holds to the CPU reference (tests/full_ref.py):
+    all but the scale and the 4 GiB cases, whose batches exist to fill the machine."""
     out = parity_cases() + worst_cases() + inplace_cases()
     n, batch = VALIDATE
     out += [Case("combine", bits, n, batch, 2, VALIDATE_TERMS, validate=True) for bits in (32, 64)]
@@ -192,8 +193,11 @@ def all_cases():
     out += [Case("tensor", bits, n, batch, 3, (), 2, False) for bits in (32, 64)
             for n, batch in HOST]
     out += [f.case for f in footprint_cases()]
-    out += scale_cases()
     return out
+
+
+def all_cases():
+    return referenced_cases() + scale_cases()
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-"""Python-integer reference of include/nttmul_ctmul.h, from the header's formulas: products and
-sums in Python integers (numpy uint64 on 32-bit words, object arrays on 64-bit words), no
-transform.  And the multiplication it serves, high -> modup -> relin -> moddown, on a seeded
+"""Integer reference of include/nttmul_ctmul.h, from the header's formulas: exact products and
+sums (numpy uint64 on 32-bit words; on 64-bit words hoist_ref.mulmod -- the oracle's 128-bit C
+product on whole polynomials, Python integers on short arrays -- and sums that account for the
+wrap), no transform.  And the multiplication it serves, high -> modup -> relin -> moddown, on a seeded
 zero-noise relinearisation key.  No GPU, but for composition(), which runs the calls of the
 contexts it is handed."""
 from functools import lru_cache
@@ -30,11 +31,27 @@ def _m(m):
     return np.uint64(m) if m < (1 << 32) else m
 
 
+def _mulmod(x, y, m):
+    """x y mod m for canonical arrays that broadcast, exact, as uint64: the 64-bit product below
+    2^32, hoist_ref.mulmod above (the oracle's 128-bit C product on whole polynomials, Python
+    integers on short arrays)."""
+    x, y = np.broadcast_arrays(np.asarray(x).astype(np.uint64), np.asarray(y).astype(np.uint64))
+    return H.mulmod(x, y, m)
+
+
+def _addmod(a, b, m):
+    """a + b mod m for canonical uint64 arrays and any m < 2^64: the sum wraps exactly when it is
+    below a."""
+    s = a + b
+    return np.where((s < a) | (s >= np.uint64(m)), s - np.uint64(m), s)
+
+
 def _dot(xs, ys, m):
-    """sum over the leading axis of xs[s] ys[s] mod m: [pairs, .., n] -> [.., n], wide."""
-    acc = _wide(np.zeros(xs.shape[1:], dtype=np.uint64), m)
+    """sum over the leading axis of xs[s] ys[s] mod m: [pairs, .., n] -> [.., n], uint64."""
+    acc = None
     for x, y in zip(xs, ys):
-        acc = (acc + _wide(x, m) * _wide(y, m) % _m(m)) % _m(m)
+        t = _mulmod(x, y, m)
+        acc = t if acc is None else _addmod(acc, t, m)
     return acc
 
 
@@ -49,7 +66,7 @@ def tensor(x_hat, y_hat, q):
         # [pairs, batch, n]: the pairs lead, _dot sums over them
         x0, x1, y0, y1 = (np.moveaxis(v[:, :, i, l], 1, 0) for v in (x_hat, y_hat) for i in (0, 1))
         out[0][:, l] = _dot(x0, y0, m)
-        out[1][:, l] = (_dot(x0, y1, m) + _dot(x1, y0, m)) % _m(m)
+        out[1][:, l] = _addmod(_dot(x0, y1, m), _dot(x1, y0, m), m)
         out[2][:, l] = _dot(x1, y1, m)
     return out
 
@@ -64,7 +81,8 @@ def add_scaled(key_sum, e0, e1, q, p):
     out = np.array(key_sum)
     for l, (m, pq) in enumerate(zip(q, p_mod(q, p))):
         for i, e in enumerate((e0, e1)):
-            out[:, i, l] = (_wide(key_sum[:, i, l], m) + _wide(e[:, l], m) * _m(pq) % _m(m)) % _m(m)
+            scaled = _mulmod(e[:, l], np.uint64(pq), m)
+            out[:, i, l] = _addmod(np.asarray(key_sum[:, i, l]).astype(np.uint64), scaled, m)
     return out
 
 

@@ -24,7 +24,32 @@ def mulmod(x, y, q):
     """x * y mod q for canonical uint64 arrays."""
     if q < (1 << 32):               # the product of two residues fits 64 bits
         return x * y % np.uint64(q)
+    if x.size >= MULMOD_C_WORDS:    # the oracle's 128-bit product, one C loop over all words
+        x, y = np.broadcast_arrays(x, y)
+        return mulmod_c(x, y, q)
+    return mulmod_py(x, y, q)
+
+
+MULMOD_C_WORDS = 2048               # below: Python integers, cheap at the small degrees
+
+
+def mulmod_py(x, y, q):
+    """x * y mod q in Python integers, whatever q."""
     return ((x.astype(object) * y.astype(object)) % q).astype(np.uint64)
+
+
+def mulmod_c(x, y, q):
+    """x * y mod q by the oracle's pointwise product (oracle/nttmul_oracle.c orc_mul_batch: one
+    unsigned 128-bit product and remainder per word), for canonical arrays of one shape.
+    tests/test_full_ref.py holds it to mulmod_py."""
+    x = np.ascontiguousarray(x, dtype=np.uint64)
+    y = np.ascontiguousarray(y, dtype=np.uint64)
+    assert x.shape == y.shape
+    out = np.empty_like(x)
+    u64p = O._u64p
+    O.lib().orc_mul_batch(out.ctypes.data_as(u64p), x.ctypes.data_as(u64p),
+                          y.ctypes.data_as(u64p), x.size, q)
+    return out
 
 
 def forward(x, moduli):

@@ -37,7 +37,6 @@ BATCHES = (3, 33)
 SHAPES = ((1, 1, 1), (4, 2, 2), (5, 2, 2), (5, 3, 5), (6, 1, 1), (3, 2, 2), (12, 4, 5))
 WIDE = ((60, 4, 15),)                        # batch 1
 DEGREE_SHAPE = (4, 2, 2)                     # every n, batch 2 (1 at 65536)
-REF_MAX_N = 512                              # cases also held to ksntt_ref
 RANGE_N = (256, 4096, 8192)                  # worst-case ranges, RANGE_SHAPE, batch 2
 RANGE_SHAPE = (5, 2, 2)
 RANGE_FILLS = ("top", "worst", "zero")
@@ -220,7 +219,9 @@ def large_cases():
     return out
 
 
-def all_cases():
+def referenced_cases():
+    """The cases whose every output word a GPU test holds to the CPU reference (tests/full_ref.py):
+    all but the scale and the 4 GiB cases, whose batches exist to fill the machine."""
     out = modup_cases() + mac_cases() + mac_worst_cases() + subbatch_cases()
     out += [Up(bits, n, 2, *RANGE_SHAPE) for bits in (32, 64) for n in RANGE_N]
     n, batch, shape = VALIDATE
@@ -230,8 +231,11 @@ def all_cases():
     out += [Mac(bits, n, batch, *HOST_SHAPE[:2], 2, 2, (5, 1)) for bits in (32, 64)
             for n, batch in HOST]
     out += [f.case for f in footprint_cases()]
-    out += scale_cases() + large_cases()
     return out
+
+
+def all_cases():
+    return referenced_cases() + scale_cases() + large_cases()
 
 
 # ---------------------------------------------------------------------------------------------

@@ -55,6 +55,30 @@ def mac(a_hat, b_hat, ks, moduli):
     out = np.empty((batch, rots, comps, M, n), dtype=a_hat.dtype)
     for r, k in enumerate(ks):
         src = galois_ref.np_tables(n, int(k))[2]
+        ar = a_hat[..., src].astype(np.uint64)
+        for l, m in enumerate(moduli):
+            if m >= 1 << 63:                                       # acc + product may pass 2^64
+                out[:, r, :, l] = mac_python(a_hat[:, :, l:l + 1], b_hat[r:r + 1, :, :, l:l + 1],
+                                             (k,), (m,))[:, 0, :, 0]
+                continue
+            for i in range(comps):
+                acc = np.zeros((batch, n), dtype=np.uint64)
+                for t in range(terms):                             # every batch entry at once
+                    bt = np.broadcast_to(b_hat[r, i, t, l].astype(np.uint64), (batch, n))
+                    acc = (acc + H.mulmod(np.ascontiguousarray(ar[:, t, l]), bt, m)) % np.uint64(m)
+                out[:, r, i, l] = acc.astype(a_hat.dtype)
+    return out
+
+
+def mac_python(a_hat, b_hat, ks, moduli):
+    """mac with every product and sum in Python integers (object arrays): what mac's exact 64-bit
+    arithmetic is held to (tests/test_ksntt_ref.py)."""
+    a_hat, b_hat = np.asarray(a_hat), np.asarray(b_hat)
+    batch, terms, M, n = a_hat.shape
+    rots, comps = b_hat.shape[:2]
+    out = np.empty((batch, rots, comps, M, n), dtype=a_hat.dtype)
+    for r, k in enumerate(ks):
+        src = galois_ref.np_tables(n, int(k))[2]
         ar = a_hat[..., src].astype(object)
         for l, m in enumerate(moduli):
             bl = b_hat[r, :, :, l].astype(object)                  # [comps, terms, n]

@@ -22,7 +22,6 @@ VIEW = (L_TOP, TOP_TERMS)
 LEVELS = (5, 4, 3, 1)
 PROFILE = {32: "chain32", 64: "chain64"}      # mixed, unsorted limb sizes
 ALL_N = (256, 512, 8192)
-REF_MAX_N = 512                               # the Python-integer references run up to here
 COMPS = (1, 2)
 ROTS = (1, 3)
 PAIRS = (1, 3)
@@ -200,9 +199,15 @@ def scale_cases():
     return out
 
 
+def referenced_cases():
+    """The cases whose every output word a GPU test holds to the CPU reference (tests/full_ref.py)
+    of the dense call on the gathered operand: the parity cases and the clean call of the
+    validate cases, at every n."""
+    return parity_cases() + validate_cases()
+
+
 def all_cases():
-    return (parity_cases() + validate_cases() + [f.case for f in footprint_cases()]
-            + scale_cases())
+    return referenced_cases() + [f.case for f in footprint_cases()] + scale_cases()
 
 
 # Kernels of libnttmul_level.so beyond libnttmul_xconv.so's that no call can launch.  None:

@@ -24,7 +24,6 @@ PARITY_N = (256, 512, 4096, 8192, 65536)
 BATCHES = (1, V + 1, 2 * V - 1)
 SHAPES = ((1, 1), (4, 2), (12, 4))           # (L, K)
 BIG_N, BIG_SHAPE, BIG_MAX_ROTS = 65536, (2, 1), 3
-REF_MAX_N = 512                              # cases also held to lintrans_ref
 WORST_N = (256, 4096)
 WORST = (16, 16, 2)                          # rots, terms, comps
 WORST_SHAPE = (2, 1)
@@ -161,15 +160,20 @@ def large_case():
     return Case(bits, n, LARGE_BYTES // per + 1, L, K, terms, comps, ks, True, True)
 
 
-def all_cases():
+def referenced_cases():
+    """The cases whose every output word a GPU test holds to the CPU reference (tests/full_ref.py):
+    all but the scale and the 4 GiB cases, whose batches exist to fill the machine."""
     out = parity_cases() + worst_cases()
     n, batch, (L, K) = VALIDATE
     out += [Case(bits, n, batch, L, K, 2, 1, (5,), True, True, True) for bits in (32, 64)]
     out += [Case(bits, n, batch, *HOST_SHAPE, 2, 2, (5, 1), True, True) for bits in (32, 64)
             for n, batch in HOST]
     out += [f.case for f in footprint_cases()]
-    out += scale_cases() + [large_case()]
     return out
+
+
+def all_cases():
+    return referenced_cases() + scale_cases() + [large_case()]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -36,7 +36,6 @@ WIDE = ((60, 4), (1, 63))                    # batch 1
 CADENCE_K = {32: (1, 2, 3, 5, 9), 64: (3, 4, 5, 17)}
 CADENCE_L = 2
 DEGREE_SHAPE = (4, 2)                        # every n, batch 2 (1 at 65536)
-REF_MAX_N = 512                              # cases also held to mdntt_ref
 RANGE_N = (256, 4096, 8192)                  # worst-case ranges, (L, K) = RANGE_SHAPE, batch 2
 RANGE_SHAPE = (3, 2)
 RANGE_FILLS = ("top", "zero_p", "zero_q")
@@ -150,7 +149,9 @@ def large_batch(bits, n, L, K):
     return LARGE_BYTES // ((L + K) * n * (bits // 8)) + 1
 
 
-def all_cases():
+def referenced_cases():
+    """The cases whose every output word a GPU test holds to the CPU reference (tests/full_ref.py):
+    all but the scale and the 4 GiB cases, whose batches exist to fill the machine."""
     out = parity_cases() + subbatch_cases()
     out += [Case(bits, n, 2, *RANGE_SHAPE) for bits in (32, 64) for n in RANGE_N]
     out += [Case(bits, n, RESCALE_BATCH, L, 1) for bits in (32, 64) for n, L in RESCALE]
@@ -158,7 +159,11 @@ def all_cases():
     out += [Case(bits, n, batch, *shape, True) for bits in (32, 64)]
     out += [Case(bits, n, batch, *HOST_SHAPE) for bits in (32, 64) for n, batch in HOST]
     out += [f.case for f in footprint_cases()]
-    out += scale_cases()
+    return out
+
+
+def all_cases():
+    out = referenced_cases() + scale_cases()
     out += [Case(bits, n, large_batch(bits, n, L, K), L, K) for bits, n, L, K in LARGE]
     return out
 

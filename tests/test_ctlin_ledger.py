@@ -133,7 +133,7 @@ def test_mirror_restates_the_selection_and_the_grid():
 
 def test_the_cases_cover_what_the_issue_names():
     rows = C.parity_cases()
-    assert C.PARITY_N == (256, 512, 4096, 8192) and C.REF_MAX_N == 512 and C.L == 3
+    assert C.PARITY_N == (256, 512, 4096, 8192) and set(rows) <= set(C.referenced_cases()) and C.L == 3
     for bits in (32, 64):
         for n in C.PARITY_N:
             mine = [c for c in rows if (c.bits, c.n, c.op) == (bits, n, "combine")]
@@ -204,3 +204,20 @@ def test_every_exported_function_that_writes_caller_memory_has_a_footprint_row()
     for f in rows:
         for per, units, words in C.units_per_block(f.case).values():
             assert C.fp_guard_words(f.case) >= max(per * words, G.guard_words(1))
+
+
+def test_every_additional_kernel_is_launched_by_a_case_held_to_the_cpu_reference(level, ctlin):
+    """The mirror reports the cases whose every output word a GPU test compares with the CPU
+    reference (referenced_cases(): at every n, tests/full_ref.py); the cases full_ref.SUBSET holds
+    on a part of their batch only do not count, and are at most one in ten.  Every kernel this
+    library adds over its predecessor is launched by one of the rest."""
+    import full_ref
+    cases = C.referenced_cases()
+    assert cases and all(c in C.all_cases() for c in cases[:8] + cases[-8:])
+    whole = [c for c in cases if not full_ref.on_subset("ctlin", c)]
+    assert 10 * (len(cases) - len(whole)) <= len(cases)
+    held = {k for c in whole for k in C.kernels_of(c)}
+    excused = {k for k in ctlin if any(re.fullmatch(pat, k) for pat, _ in
+                                        getattr(C, "UNREACHABLE", ()))}
+    extra = set(ctlin) - set(level)
+    assert extra and sorted(extra - held - excused) == []

@@ -149,7 +149,7 @@ def test_the_cases_cover_what_the_issue_names():
             assert {(c.n, c.pairs, c.terms) for c in C.worst_cases()
                     if c.bits == bits and c.op == op} == {(n, 16, 16) for n in (256, 4096)}
     assert (C.V + 1) % C.V and (2 * C.V - 1) % C.V and C.V + 1 > C.V  # a partial and a full workgroup
-    assert C.CHAIN_N == (256, 8192) and C.REF_MAX_N == 512
+    assert C.CHAIN_N == (256, 8192) and set(C.parity_cases()) <= set(C.referenced_cases())
     big = C.large_case()
     per = big.terms * (big.L + big.K) * big.n * (big.bits // 8)
     assert big.op == "relin" and big.batch * per > 1 << 32 >= (big.batch - 1) * per
@@ -217,3 +217,20 @@ def test_every_exported_function_has_a_footprint_row_or_a_reason():
     for f in rows:
         for per, units, words in C.units_per_block(f.case).values():
             assert C.fp_guard_words(f.case) >= max(per * words, G.guard_words(1))
+
+
+def test_every_additional_kernel_is_launched_by_a_case_held_to_the_cpu_reference(lintrans, ctmul):
+    """The mirror reports the cases whose every output word a GPU test compares with the CPU
+    reference (referenced_cases(): at every n, tests/full_ref.py); the cases full_ref.SUBSET holds
+    on a part of their batch only do not count, and are at most one in ten.  Every kernel this
+    library adds over its predecessor is launched by one of the rest."""
+    import full_ref
+    cases = C.referenced_cases()
+    assert cases and all(c in C.all_cases() for c in cases[:8] + cases[-8:])
+    whole = [c for c in cases if not full_ref.on_subset("ctmul", c)]
+    assert 10 * (len(cases) - len(whole)) <= len(cases)
+    held = {k for c in whole for k in C.kernels_of(c)}
+    excused = {k for k in ctmul if any(re.fullmatch(pat, k) for pat, _ in
+                                        getattr(C, "UNREACHABLE", ()))}
+    extra = set(ctmul) - set(lintrans)
+    assert extra and sorted(extra - held - excused) == []

@@ -2,9 +2,10 @@
 limbs (include/nttmul_ctlin.h, lib/libnttmul_ctlin.so, csrc/ctlin_dev.hpp k_ctlin_combine and
 k_ctlin_tensor).
 
-Every comparison is bit for bit.  Up to n = 512 the reference is Python integers
-(tests/ctlin_ref.py); above, the composition the call replaces: one plain pointwise context per
-limb plus host modular additions.  Operands are device-resident between sentinel guards, aligned
+Every comparison is bit for bit.  At every degree the expected value of every output word is the
+CPU reference (tests/full_ref.py over tests/ctlin_ref.py), which shares no code with the device;
+above n = 512 the composition the call replaces -- one plain pointwise context per limb plus host
+modular additions -- is compared beside it and says which side is wrong.  Operands are device-resident between sentinel guards, aligned
 to their word only, every output preset to the sentinel (tests/guarded.py).  L = 3 on the
 mixed-size chains of tests/basis_cases.py, both word classes; the shapes are the smallest at which
 the kernels can go wrong (tests/ctlin_cases.py).  Any canonical vector is a transform of
@@ -18,6 +19,7 @@ import pytest
 import bconv_ref as B
 import ctlin_cases as C
 import ctlin_ref as ref
+import full_ref as F
 import guarded as G
 import nttmul
 
@@ -130,12 +132,15 @@ class _Plain:
 
 
 def _want_combine(case, xs, ws):
-    """Python integers up to REF_MAX_N, the composition a caller runs today above."""
+    """The CPU reference of every output word (tests/full_ref.py) at every n; above n = 512 the
+    composition a caller runs today is held to it as well, which says which side is wrong."""
     q, terms = C.moduli_of(case), _ref_terms(case, xs, ws)
-    if case.n <= C.REF_MAX_N:
-        return ref.combine(terms, q, _shape(case), _dt(case.bits))
-    with _Plain(case.n, q) as plain:
-        return ref.composition(plain, terms, q, _shape(case), _dt(case.bits))
+    want = F.reference("ctlin", "combine", terms, q, _shape(case), _dt(case.bits))
+    if case.n > 512:
+        with _Plain(case.n, q) as plain:
+            F.assert_equal(ref.composition(plain, terms, q, _shape(case), _dt(case.bits)), want,
+                           ("the composition", _id(case)))
+    return want
 
 
 def _id(c):
@@ -159,9 +164,8 @@ def test_parity(case, torch_cuda):
             return
         x, y = _pairs(case, case.n + case.batch + case.pairs)
         got = _tensor(torch_cuda, cl, x, y)
-    if case.n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.tensor(x, y, q))
-    else:
+    F.assert_equal(got, F.reference("ctlin", "tensor", x, y, q), _id(case))
+    if case.n > 512:
         with _Plain(case.n, q) as plain:
             assert np.array_equal(got, ref.tensor_composition(plain, x, y, q))
     # d_2 is nttmul_ctmul_high's output bit for bit
@@ -188,6 +192,8 @@ def test_worst_case_fill(case, torch_cuda):
         got = _combine(torch_cuda, cl, case, [x] * 16, [w] * 16)
         zero = _combine(torch_cuda, cl, case, [np.zeros_like(x)] * 16, [w] * 16)
     assert not zero.any()
+    terms = [(x, w if kind == C.PLAIN else None, C.KIND_CODE[kind])] * 16
+    F.assert_equal(got, F.reference("ctlin", "combine", terms, q, _shape(case), dt), _id(case))
     for l, m in enumerate(q):
         assert (got[:, :, l] == (16 if kind == C.PLAIN else -16) % m).all(), l
 
@@ -296,6 +302,7 @@ def test_host_form_equals_the_device_form(n, batch, bits, torch_cuda):
             td = _tensor(torch_cuda, cl, x, yy)
             th = cl.tensor(x, yy)
             assert th.dtype == dt and np.array_equal(th, td)
+            F.assert_equal(td, F.reference("ctlin", "tensor", x, yy, q), (n, batch, bits))
         assert cl.tensor(x[:0], y[:0]).shape == (0, 3, C.L, n)
         assert cl.combine([(xs[0][:0], None, 0)]).shape == (0, 2, C.L, n)
         with pytest.raises(ValueError):

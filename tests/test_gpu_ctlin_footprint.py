@@ -17,6 +17,7 @@ import pytest
 import bconv_ref as B
 import ctlin_cases as C
 import ctlin_ref as ref
+import full_ref as F
 import guarded as G
 import nttmul
 
@@ -66,18 +67,24 @@ def _ptr(view, host):
 
 
 def _reference(case, terms, x, y, q, dt):
-    """Python integers at n <= REF_MAX_N, the composition of existing calls above."""
+    """The CPU reference of every output word (tests/full_ref.py) at every n; above n = 512 the
+    composition of existing calls is held to it as well, which says which side is wrong."""
     shape = (case.batch, case.comps, C.L, case.n)
-    if case.n <= C.REF_MAX_N:
-        return ref.combine(terms, q, shape, dt) if case.op == "combine" else ref.tensor(x, y, q)
+    want = F.reference("ctlin", "combine", terms, q, shape, dt) if case.op == "combine" else \
+        F.reference("ctlin", "tensor", x, y, q)
+    if case.n <= 512:
+        return want
     plain = [nttmul.Context(case.n, m) for m in q]
     try:
         if case.op == "combine":
-            return ref.composition(plain, terms, q, shape, dt)
-        return ref.tensor_composition(plain, x, y, q)
+            comp = ref.composition(plain, terms, q, shape, dt)
+        else:
+            comp = ref.tensor_composition(plain, x, y, q)
     finally:
         for c in plain:
             c.close()
+    F.assert_equal(comp, want, ("the composition", case))
+    return want
 
 
 @pytest.mark.gpu

@@ -6,7 +6,11 @@ ends in a partial last workgroup (at n = 256 a workgroup takes 4 batch entries o
 2 on 64-bit words).  Inputs are made on the device, the output is preset to a sentinel no
 canonical word equals, every word is compared on the device with the per-limb composition (the
 plain contexts' pointwise products, device additions) and the structural sample of scale_cases
-with tests/ctlin_ref.py in Python integers."""
+with tests/ctlin_ref.py in Python integers.
+
+The batches here exist to fill the machine (at least 16384 waves per launch), so an integer
+reference of every output word would be minutes of CPU: this file keeps its sampled check.  The CPU
+reference of every output word, at every degree, is held in test_gpu_ctlin.py (tests/full_ref.py)."""
 import numpy as np
 import pytest
 

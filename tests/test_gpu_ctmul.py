@@ -3,8 +3,10 @@ lib/libnttmul_ctmul.so, csrc/ctmul_dev.hpp k_ctmul_high and k_ctmul_relin).
 
 Every case is compared bit for bit with the composition of existing calls it replaces
 (tests/ctmul_ref.py composition): ksntt_mac with k = (1,) for the key sum, the per-limb pointwise
-products of one plain context per limb of Q for the tensor terms, host modular additions.  Up to
-n = 512 also with the Python-integer reference.  Operands are device-resident between sentinel
+products of one plain context per limb of Q for the tensor terms, host modular additions.  And, on
+every output word at every degree, with the CPU reference (tests/full_ref.py over
+tests/ctmul_ref.py), which shares no code with the device: the composition beside it says which
+side is wrong.  Operands are device-resident between sentinel
 guards, aligned to their word only, every output preset to the sentinel (tests/guarded.py).  The
 shapes are the smallest at which the kernels can go wrong (tests/ctmul_cases.py).  Any canonical
 vector is a transform of something, so the inputs are seeded canonical words."""
@@ -14,6 +16,7 @@ import pytest
 import bconv_ref as B
 import ctmul_cases as C
 import ctmul_ref as ref
+import full_ref as F
 import guarded as G
 import hoist_cases as HC
 import mdntt_ref
@@ -130,14 +133,12 @@ def test_parity(case, torch_cuda):
         if case.op == "high":
             got = _high(torch_cuda, ct, x, y)
             assert np.array_equal(got, ref.tensor_composition(plain, x, y, q)[2])
-            if case.n <= C.REF_MAX_N:
-                assert np.array_equal(got, ref.high(x, y, q))
+            F.assert_equal(got, F.reference("ctmul", "high", x, y, q), _id(case))
             return
         got = _relin(torch_cuda, ct, up, key, x, y)
         with nttmul.NttKeySwitch(case.n, q, p, 1) as kn:
             assert np.array_equal(got, ref.composition(kn, plain, up, key, x, y, q, p))
-    if case.n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.relin(up, key, x, y, q, p))
+    F.assert_equal(got, F.reference("ctmul", "relin", up, key, x, y, q, p), _id(case))
 
 
 @pytest.mark.parametrize("case", C.worst_cases(), ids=_id)
@@ -157,6 +158,8 @@ def test_worst_case_ranges(fill, case, torch_cuda):
     with nttmul.NttCtMul(n, q, p) as ct:
         got = _high(torch_cuda, ct, x, y) if case.op == "high" else \
             _relin(torch_cuda, ct, up, key, x, y)
+    F.assert_equal(got, F.reference("ctmul", "high", x, y, q) if case.op == "high" else
+                   F.reference("ctmul", "relin", up, key, x, y, q, p), (_id(case), fill))
     if fill == "zero":
         assert not got.any()
         return
@@ -231,17 +234,17 @@ def _device_chain(torch, n, ch, pairs_of=None):
 @pytest.mark.parametrize("n", C.CHAIN_N)
 def test_the_multiplication_end_to_end(n, bits, torch_cuda):
     """high -> NttKeySwitch.modup -> relin -> NttModDown.moddown on hoist_cases.CHAIN_SHAPE with a
-    ternary s of weight CHAIN_H and the zero-noise key for s s -> s: at n = 256 every stage bit
-    for bit the Python-integer chain's; at both n the result decrypts to d0 + d1 s + d2 s^2 within
+    ternary s of weight CHAIN_H and the zero-noise key for s s -> s: at both n every stage bit
+    for bit the CPU chain's, the NTT-domain ones word for word; the result decrypts to d0 + d1 s + d2 s^2 within
     +-(K + 1)(1 + h) per limb, centred.  The bound is derived (tests/ctmul_ref.py chain_bound):
     with a zero-noise key c_hat[0] + c_hat[1] s = P (d0 + d1 s + d2 s^2) mod QP exactly, and
     ModDown's output is (Y_i - r_i) / P with 0 <= r_i < (K + 1) P: one key switch's rounding."""
-    small = n <= C.REF_MAX_N
-    ch = ref.chain(n, bits) if small else ref.chain_inputs(n, bits)
+    ch = ref.chain(n, bits)
     got = _device_chain(torch_cuda, n, ch)
-    if small:
-        for stage in ("x_hat", "y_hat", "key_hat", "d2_hat", "up_hat", "mid", "out", "d"):
-            assert np.array_equal(got[stage], ch[stage]), stage
+    for stage in ("x_hat", "y_hat", "key_hat", "d2_hat", "up_hat", "mid", "out", "d"):
+        F.assert_equal(got[stage], ch[stage], stage)
+    F.assert_equal(got["out_hat"], mdntt_ref.forward(ch["out"].reshape(-1, len(ch["q"]), n),
+                                                     ch["q"]), "out_hat")
     errs = ref.chain_errors(ch, got["out"], got["d"])
     L, K, _ = HC.CHAIN_SHAPE
     print("ctmul chain errors", n, bits, errs, "bound", ref.chain_bound())
@@ -343,10 +346,12 @@ def test_host_form_equals_the_device_form(n, batch, bits, torch_cuda):
             host = ct.relin(up, key, x, yy)
             assert host.dtype == _dt(bits) and np.array_equal(host, dev)
             assert np.array_equal(dev, ref.composition(kn, plain, up, key, x, yy, q, p))
+            F.assert_equal(dev, F.reference("ctmul", "relin", up, key, x, yy, q, p), (n, bits))
             hd = _high(torch_cuda, ct, x, yy)
             hh = ct.high(x, yy)
             assert hh.dtype == _dt(bits) and np.array_equal(hh, hd)
             assert np.array_equal(hd, ref.tensor_composition(plain, x, yy, q)[2])
+            F.assert_equal(hd, F.reference("ctmul", "high", x, yy, q), (n, bits))
         assert ct.relin(up[:0], key, x[:0], y[:0]).shape == (0, 2, L + K, n)
         assert ct.high(x[:0], y[:0]).shape == (0, L, n)
         with pytest.raises(ValueError):

@@ -16,6 +16,7 @@ import pytest
 import bconv_ref as B
 import ctmul_cases as C
 import ctmul_ref as ref
+import full_ref as F
 import guarded as G
 import nttmul
 
@@ -116,15 +117,21 @@ def test_calls(param, torch_cuda):
 
 
 def _reference(op, n, up, key, x, y, q, p):
-    """Python integers at n <= REF_MAX_N, the composition of existing calls above."""
-    if n <= C.REF_MAX_N:
-        return ref.high(x, y, q) if op == "high" else ref.relin(up, key, x, y, q, p)
+    """The CPU reference of every output word (tests/full_ref.py) at every n; above n = 512 the
+    composition of existing calls is held to it as well, which says which side is wrong."""
+    want = F.reference("ctmul", "high", x, y, q) if op == "high" else \
+        F.reference("ctmul", "relin", up, key, x, y, q, p)
+    if n <= 512:
+        return want
     plain = [nttmul.Context(n, m) for m in q]
     try:
         if op == "high":
-            return ref.tensor_composition(plain, x, y, q)[2]
-        with nttmul.NttKeySwitch(n, q, p, 1) as kn:
-            return ref.composition(kn, plain, up, key, x, y, q, p)
+            comp = ref.tensor_composition(plain, x, y, q)[2]
+        else:
+            with nttmul.NttKeySwitch(n, q, p, 1) as kn:
+                comp = ref.composition(kn, plain, up, key, x, y, q, p)
     finally:
         for c in plain:
             c.close()
+    F.assert_equal(comp, want, ("the composition", op, n))
+    return want

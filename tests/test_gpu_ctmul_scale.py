@@ -7,7 +7,11 @@ workgroup at this n).  Inputs are made on the device, the output is preset to a 
 canonical word equals, every word is compared on the device with the composition of existing
 calls (ksntt_mac with k = (1,), the plain contexts' pointwise products, device additions) and the
 structural sample of scale_cases with tests/ctmul_ref.py.  A further test passes an up_hat just
-over 4 GiB and compares with the same call in chunks below 1 GiB."""
+over 4 GiB and compares with the same call in chunks below 1 GiB.
+
+The batches here exist to fill the machine (at least 16384 waves per launch), so an integer
+reference of every output word would be minutes of CPU: this file keeps its sampled check.  The CPU
+reference of every output word, at every degree, is held in test_gpu_ctmul.py (tests/full_ref.py)."""
 import numpy as np
 import pytest
 

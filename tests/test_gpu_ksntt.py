@@ -6,7 +6,9 @@ Every case is compared bit for bit with the device composition it replaces:
   (B) mac(a_hat, b_hat, k) == forward(hoist_ntt(a_hat, b_hat, k)),
   (C) mdntt_moddown(mac(modup(x_hat), key_hat, k)) == forward of the coefficient-order chain's
       output, on hoist_ref.chain's keys, within its bound +-(K + 1)(1 + h),
-and up to n = 512 with the Python-integer reference tests/ksntt_ref.py as well.  Operands are
+and, on every output word at every degree, with the CPU reference (tests/full_ref.py over
+tests/ksntt_ref.py and the oracle's transforms), which shares no code with the device: the
+compositions beside it say which side is wrong when the two disagree.  Operands are
 device-resident, every output is preset to the sentinel (tests/guarded.py for the small cases, a
 fill for the large ones).  The shapes are the smallest at which the kernels can go wrong
 (tests/ksntt_cases.py).  Any canonical vector is a transform of something, so the inputs are
@@ -15,6 +17,7 @@ import numpy as np
 import pytest
 
 import bconv_ref as B
+import full_ref as F
 import guarded as G
 import hoist_ref as H
 import ks_ref
@@ -150,8 +153,7 @@ def test_modup_parity(case, torch_cuda):
     assert np.array_equal(got, _compose_modup(torch_cuda, case.n, q, p, case.alpha, x))
     for d, D in enumerate(ks_ref.digits(case.L, case.alpha)):     # the own limbs are copies
         assert np.array_equal(got[:, d, D.start:D.stop], x[:, D.start:D.stop])
-    if case.n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.modup(x, q, p, case.alpha))
+    F.assert_equal(got, F.reference("ksntt", "modup", x, q, p, case.alpha), _up_id(case))
 
 
 @pytest.mark.parametrize("bits", (32, 64))
@@ -180,8 +182,9 @@ def test_modup_worst_case_ranges(fill, n, bits, torch_cuda):
     assert np.array_equal(got, _compose_modup(torch_cuda, n, q, p, alpha, x))
     if fill == "zero":
         assert not got.any()
-    if n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.modup(x, q, p, alpha))
+    if fill == "worst":
+        assert np.array_equal(x, ref.worst_x_hat(q, alpha, 2, n, _dt(bits)))
+    F.assert_equal(got, F.reference("ksntt", "modup", x, q, p, alpha), (fill, n, bits))
 
 
 def test_modup_sub_batches_and_two_streams(torch_cuda):
@@ -195,13 +198,19 @@ def test_modup_sub_batches_and_two_streams(torch_cuda):
         with nttmul.NttKeySwitch(case.n, q, p, case.alpha, scratch_mb=1) as kn:
             assert kn.info.scratch_mb == 1
             small = _x(case._replace(batch=1), 3)
-            assert np.array_equal(_modup(torch, kn, small),
-                                  _compose_modup(torch, case.n, q, p, case.alpha, small))
+            got = _modup(torch, kn, small)
+            assert np.array_equal(got, _compose_modup(torch, case.n, q, p, case.alpha, small))
+            F.assert_equal(got, F.reference("ksntt", "modup", small, q, p, case.alpha),
+                           (case, "one polynomial"))
             x = _x(case, 4)                     # the scratch grows to a whole sub-batch
             want_x = _compose_modup(torch, case.n, q, p, case.alpha, x)
             assert np.array_equal(_modup(torch, kn, x), want_x)
+            F.assert_equal(want_x, F.reference("ksntt", "modup", x, q, p, case.alpha),
+                           (case, "sub-batches"))
             y = _x(case, 5)
             want_y = _compose_modup(torch, case.n, q, p, case.alpha, y)
+            F.assert_equal(want_y, F.reference("ksntt", "modup", y, q, p, case.alpha),
+                           (case, "second stream"))
             dx, dy = _to_dev(torch, x, bits), _to_dev(torch, y, bits)
             ox = torch.full((want_x.size,), -1, dtype=_tdt(torch, bits), device="cuda")
             oy = torch.full((want_y.size,), -1, dtype=_tdt(torch, bits), device="cuda")
@@ -225,8 +234,7 @@ def test_mac_parity(case, torch_cuda):
             C.kernel_name("mac", case.n, case.bits, case.comps)
         got = _mac(torch_cuda, kn, a, b, case.ks)
     assert np.array_equal(got, _compose_mac(torch_cuda, case.n, ext, a, b, case.ks))
-    if case.n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.mac(a, b, case.ks, ext))
+    F.assert_equal(got, F.reference("ksntt", "mac", a, b, case.ks, ext), _mac_id(case))
 
 
 @pytest.mark.parametrize("case", C.mac_worst_cases(), ids=_mac_id)
@@ -243,6 +251,7 @@ def test_mac_worst_case_input(case, torch_cuda):
         got = _mac(torch_cuda, kn, a, b, case.ks)
     assert (got == case.terms).all()
     assert np.array_equal(got, _compose_mac(torch_cuda, case.n, ext, a, b, case.ks))
+    F.assert_equal(got, F.reference("ksntt", "mac", a, b, case.ks, ext), _mac_id(case))
 
 
 @pytest.mark.parametrize("bits", (32, 64))
@@ -286,10 +295,12 @@ def test_validate_flag_leaves_the_output_untouched(bits, torch_cuda):
     a, b = _ab(mac, 10)
     with nttmul.NttKeySwitch(n, q, p, alpha, validate=True) as strict, \
             nttmul.NttKeySwitch(n, q, p, alpha) as lax:
-        assert np.array_equal(_modup(torch, strict, good),
-                              _compose_modup(torch, n, q, p, alpha, good))
-        assert np.array_equal(_mac(torch, strict, a, b, mac.ks),
-                              _compose_mac(torch, n, ext, a, b, mac.ks))
+        got = _modup(torch, strict, good)
+        assert np.array_equal(got, _compose_modup(torch, n, q, p, alpha, good))
+        F.assert_equal(got, F.reference("ksntt", "modup", good, q, p, alpha), bits)
+        got = _mac(torch, strict, a, b, mac.ks)
+        assert np.array_equal(got, _compose_mac(torch, n, ext, a, b, mac.ks))
+        F.assert_equal(got, F.reference("ksntt", "mac", a, b, mac.ks, ext), bits)
         bad = good.copy()
         bad[batch - 1, L - 1, n - 1] = q[L - 1]
         out = torch.full((batch * C.dnum(up) * (L + K) * n,), -1, dtype=_tdt(torch, bits),
@@ -337,6 +348,8 @@ def test_host_forms_equal_the_device_forms(n, batch, bits, torch_cuda):
             kn.mac(a, b[:1], mac.ks)
     assert np.array_equal(dev, _compose_modup(torch_cuda, n, q, p, alpha, x))
     assert np.array_equal(dev_c, _compose_mac(torch_cuda, n, q + p, a, b, mac.ks))
+    F.assert_equal(dev, F.reference("ksntt", "modup", x, q, p, alpha), (n, batch, bits))
+    F.assert_equal(dev_c, F.reference("ksntt", "mac", a, b, mac.ks, q + p), (n, batch, bits))
 
 
 def test_device_path_rules(torch_cuda):

@@ -4,7 +4,7 @@ the `_device` entry points and the host forms of both operations run between sen
 addresses aligned to the word and to nothing larger; afterwards no guard word has changed, every
 input is bit-identical to the copy taken before the call, exactly the output's words are written
 (the arena's output is that long, every word after it is a guard, and no word of it keeps the
-sentinel), and the result is right bit for bit (tests/ksntt_ref.py).
+sentinel), and the result is right bit for bit at every degree (tests/full_ref.py).
 
 The rows are tests/ksntt_cases.py footprint_cases(): n = 256 with batch 1 and 33 (a half-empty
 pair, partial workgroups), n = 4096 and n = 8192 with batch 1, (L, K, alpha) = (3, 2, 2) and
@@ -16,9 +16,9 @@ import numpy as np
 import pytest
 
 import bconv_ref as B
+import full_ref as F
 import guarded as G
 import ksntt_cases as C
-import ksntt_ref as ref
 import nttmul
 
 # exported functions that write no caller memory beyond a small result of fixed size
@@ -77,17 +77,18 @@ def test_modup(param, torch_cuda):
     q, p = C.moduli_of(rows[0].case)
     B_ = max(f.case.batch for f in rows)
     x = B.random_words(np.random.default_rng(n + bits + L), q, B_, n, G.dtype_of(bits))
-    # the reference once, on the rows' largest batch; above REF_MAX_N the device composition of
-    # tests/test_gpu_ksntt.py holds the values, and here the coefficient-order chain does
-    want = ref.modup(x, q, p, alpha) if n <= C.REF_MAX_N else None
+    # the CPU reference once, on the rows' largest batch, at every degree; above n = 512 the
+    # coefficient-order chain on the device beside it, which says which side is wrong
+    want = F.reference("ksntt", "modup", x, q, p, alpha)
     with nttmul.NttKeySwitch(n, q, p, alpha) as kn:
         assert kn.word_bits == bits
-        if want is None:
+        if n > 512:
             Ctx = nttmul.RnsHoistContext if n <= 4096 else nttmul.RnsMpHoistContext
             with Ctx(n, q) as low, Ctx(n, q + p) as ext, \
                     nttmul.KeySwitchBasis(n, q, p, alpha) as ks:
                 up = ks.modup(low.inverse(x))
-                want = ext.forward(up.reshape(-1, L + K, n)).reshape(up.shape)
+                chain = ext.forward(up.reshape(-1, L + K, n)).reshape(up.shape)
+            F.assert_equal(chain, want, ("the coefficient-order chain", param))
         for f in rows:
             c = f.case
             assert f.entry == "nttmul_ksntt_modup" + ("" if f.host else "_device")
@@ -122,7 +123,7 @@ def test_mac(param, torch_cuda):
     a = B.random_words(rng, ext * terms, B_, n, G.dtype_of(bits)).reshape(B_, terms, M, n)
     b = B.random_words(rng, ext * (terms * comps), len(ks), n, G.dtype_of(bits)).reshape(
         len(ks), comps, terms, M, n)
-    want = ref.mac(a, b, ks, ext)
+    want = F.reference("ksntt", "mac", a, b, ks, ext)
     karr = (ctypes.c_uint32 * len(ks))(*ks)
     with nttmul.NttKeySwitch(n, q, p, 1) as kn:
         for f in rows:

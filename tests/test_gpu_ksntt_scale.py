@@ -5,7 +5,11 @@ least 2 * 8192 waves, with the smallest batch that meets it and a partial last w
 one can exist.  Inputs are made on the device, the output is preset to a sentinel no canonical
 word equals, every word is compared on the device with the composition (inverse, ks_modup,
 forward; hoist_ntt, forward) and the scale_cases sample with tests/ksntt_ref.py.  Two further
-tests pass an output just over 4 GiB and compare with the same call in chunks below 1 GiB."""
+tests pass an output just over 4 GiB and compare with the same call in chunks below 1 GiB.
+
+The batches here exist to fill the machine (at least 16384 waves per launch), so an integer
+reference of every output word would be minutes of CPU: this file keeps its sampled check.  The CPU
+reference of every output word, at every degree, is held in test_gpu_ksntt.py (tests/full_ref.py)."""
 import numpy as np
 import pytest
 

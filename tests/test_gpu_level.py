@@ -4,8 +4,9 @@ tests/basis_cases.py (mixed, unsorted limb sizes) and the levels 5 (the identity
 partial last digit) and 1 (tests/level_cases.py).
 
 Every view call is compared bit for bit with the dense call of the same context on
-tests/level_ref.gather of the top-level operand, made on the device; up to n = 512 also with the
-Python-integer references the dense calls are held to.  A second test sets every word outside the
+tests/level_ref.gather of the top-level operand, made on the device; and, on every output word
+at every n, with the CPU reference of the dense call (tests/full_ref.py), which shares no code with
+the device.  A second test sets every word outside the
 view to all ones, out of range for every modulus: the output must not change and
 NTTMUL_FLAG_VALIDATE must pass, and one word inside the view out of range must be NTTMUL_ERANGE
 with the output untouched.  A third runs the chain end to end on zero-noise keys made once for the
@@ -16,15 +17,13 @@ import numpy as np
 import pytest
 
 import bconv_ref as B
-import ctmul_ref
+import full_ref as F
 import galois_ref
 import hoist_ref as H
 import ks_ref
-import ksntt_ref
 import level_cases as C
 import level_gpu as G
 import level_ref as LR
-import lintrans_ref
 import nttmul
 
 pytestmark = pytest.mark.gpu
@@ -39,17 +38,18 @@ def torch_cuda():
 
 
 def _reference(case, ops, key, w):
-    """The Python-integer reference of the dense call on host copies."""
+    """The CPU reference of the dense call on host copies (tests/full_ref.py)."""
     bits = case.bits
     q, p = C.level_bases(bits, case.L)
     a, key = G.host(ops["a"], bits), G.host(key, bits)
     if case.op == "mac":
-        return ksntt_ref.mac(a, key, ops["ks"], q + p)
+        return F.reference("level", "mac", a, key, ops["ks"], q + p)
     if case.op == "lintrans":
-        return lintrans_ref.apply(a, key, ops["ks"], q, p,
-                                  None if w is None else G.host(w, bits),
-                                  None if ops["c0"] is None else G.host(ops["c0"], bits))
-    return ctmul_ref.relin(a, key, G.host(ops["x"], bits), G.host(ops["y"], bits), q, p)
+        return F.reference("level", "lintrans", a, key, ops["ks"], q, p,
+                           None if w is None else G.host(w, bits),
+                           None if ops["c0"] is None else G.host(ops["c0"], bits))
+    return F.reference("level", "relin", a, key, G.host(ops["x"], bits), G.host(ops["y"], bits),
+                       q, p)
 
 
 def _groups():
@@ -84,9 +84,8 @@ def test_view_equals_the_dense_call_on_the_gathered_operand(cases, torch_cuda):
             if case.L == C.L_TOP:
                 # the identity view: the gathered operand is the operand
                 assert torch.equal(key, ops["key"])
-            if case.n <= C.REF_MAX_N:
-                ref = _reference(case, ops, key, w)
-                assert np.array_equal(G.host(got, case.bits), ref), G.case_id(case)
+            F.assert_equal(G.host(got, case.bits), _reference(case, ops, key, w),
+                           G.case_id(case))
 
 
 @pytest.mark.parametrize("case", C.validate_cases(), ids=G.case_id)
@@ -96,6 +95,8 @@ def test_words_outside_the_view_are_neither_read_nor_checked(case, torch_cuda):
     terms = ops["terms"]
     with G.context(case, validate=True) as ctx:
         clean = G.call(torch, ctx, case, ops, C.VIEW)
+        F.assert_equal(G.host(clean, case.bits), _reference(case, ops, *G.gathered(case, ops)),
+                       G.case_id(case))
         # every word outside the view all ones
         poisoned = dict(ops)
         sel = torch.from_numpy(LR.selected(tuple(ops["key"].shape), C.VIEW, case.L, terms)).cuda()

@@ -4,7 +4,11 @@ at n = 256 with three rotations, k_level_lintrans at n = 4096 with three rotatio
 c_0, k_level_relin at n = 4096 with two pairs; both word classes) holds at least 2 * 8192 waves,
 with the smallest batch that meets it and ends in a partial last workgroup.  Inputs are made on the
 device, the output is preset to a sentinel no canonical word equals, and every word is compared on
-the device with the dense call of the same context on level_ref.gather of the key."""
+the device with the dense call of the same context on level_ref.gather of the key.
+
+The batches here exist to fill the machine (at least 16384 waves per launch), so an integer
+reference of every output word would be minutes of CPU: this file keeps its sampled check.  The CPU
+reference of every output word, at every degree, is held in test_gpu_level.py (tests/full_ref.py)."""
 import pytest
 
 import level_cases as C

@@ -13,11 +13,13 @@ tests/test_gpu_lifetime.py's:
 * every status is the step's; after NTTMUL_ERANGE the output still holds the sentinel and
   last_error the range check's text.
 
-Expected values: the CPU references of limb_lifetime_cases.expected (the oracle per limb for every
-rnsmp entry, Python integers for the key mac at any n and for the conversions up to REF_MAX_N);
-at n = 8192 what each library's own parity test uses there: the device compositions of
-test_gpu_mdntt.py and test_gpu_ksntt.py through fresh contexts of other libraries, and for xconv
-the sampled composition of tests/xconv_gpu.py.
+Expected values: the CPU references of limb_lifetime_cases.expected, every output word at every n
+(the oracle per limb for every rnsmp entry, exact integers for the key mac, tests/full_ref.py for
+the conversions).  At n = 8192 what each library's own parity test compares beside it is held to
+the same values before the sequence starts: the device compositions of test_gpu_mdntt.py and
+test_gpu_ksntt.py through fresh contexts of other libraries, and for xconv the library's inverse
+of the output against the reference arithmetic on the library's inverse of the input, on every
+coefficient.
 
 Contexts are closed only after the final synchronise: destroy does not wait for caller streams."""
 import ctypes
@@ -32,8 +34,8 @@ import ksntt_ref
 import limb_lifetime_cases as L
 import mdntt_ref
 import nttmul
-import xconv_cases as XC
 import xconv_gpu as XG
+import xconv_ref
 from test_gpu_ksntt import _compose_modup
 from test_gpu_mdntt import _compose as _compose_moddown
 
@@ -114,31 +116,34 @@ class Run:
             torch.cuda.synchronize(d)
 
     def _compose(self):
-        """The expected values no CPU reference reaches, all steps of a kind in one batch."""
+        """Beside the CPU references, above n = 512: the device compositions the libraries' own
+        parity tests keep, all steps of a kind in one batch.  They are held to the CPU reference
+        here, before the sequence; for xconv verify() makes the second half."""
         torch, cp = self.torch, self.cp
         todo = [(s, io) for s, io in zip(self.steps, self.io)
-                if io["want"] is None and s.status == "OK"]
+                if s.status == "OK" and cp.n > 512 and cp.lib in ("mdntt", "ksntt", "xconv")
+                and s.entry in ("moddown", "modup", "extend")]
         if not todo:
             return
-        assert cp.n > L.REF_MAX_N
         q, p = L.moduli_of(cp)
         for entry in sorted({s.entry for s, _ in todo}):
             group = [io for s, io in todo if s.entry == entry]
             x = np.concatenate([io["ops"]["a"] for io in group])
             if cp.lib == "mdntt":
-                want = _compose_moddown(torch, cp.n, q, p, x)
+                comp = _compose_moddown(torch, cp.n, q, p, x)
             elif cp.lib == "ksntt":
-                want = _compose_modup(torch, cp.n, q, p, cp.shape[2], x)
+                comp = _compose_modup(torch, cp.n, q, p, cp.shape[2], x)
             else:
-                # xconv_gpu.check_composition's first half; verify() makes the second
-                idx = XC.sample_indices(cp.n)
                 with XG.ctx(cp.n)(cp.n, tuple(p) if entry == "extend" else tuple(q) + tuple(p)) as wide:
                     coef = wide.inverse(x)
-                want = XG.want_sampled(entry, coef, q, p, cp.shape[2], idx)
+                comp = getattr(xconv_ref, entry + "_coeff")(coef, q, p, cp.shape[2])
             at = 0
             for io in group:
                 b = io["ops"]["a"].shape[0]
-                io["want"], io["sampled"] = want[at:at + b], cp.lib == "xconv"
+                if cp.lib == "xconv":
+                    io["coef"] = comp[at:at + b]
+                else:
+                    assert np.array_equal(comp[at:at + b], io["want"]), (self.name, entry, "composition")
                 at += b
 
     def _place(self, step, io):
@@ -250,14 +255,14 @@ class Run:
                 assert (got == sentinel).all(), (where, "output written by a failed call")
                 continue
             want = io["want"]
-            if io.get("sampled"):               # xconv_gpu.check_composition's second half
-                if low is None:
-                    low = XG.ctx(cp.n)(cp.n, L.moduli_of(cp)[0])
-                got = low.inverse(got)[:, :, XC.sample_indices(cp.n)]
             assert got.shape == want.shape and got.dtype == want.dtype, where
             rows = got.reshape(got.shape[0], -1) != want.reshape(want.shape[0], -1)
             bad = np.flatnonzero(rows.any(axis=1))
             assert bad.size == 0, (where, f"{bad.size} batch entries differ, first {bad[:4]}")
+            if "coef" in io:                    # the composition's second half, every coefficient
+                if low is None:
+                    low = XG.ctx(cp.n)(cp.n, L.moduli_of(cp)[0])
+                assert np.array_equal(low.inverse(got), io["coef"]), (where, "composition")
         if low is not None:
             low.close()
 

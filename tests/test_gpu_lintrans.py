@@ -5,8 +5,9 @@ Every case is compared bit for bit with the device composition of existing calls
 m = ksntt_mac(a_hat, b_hat, k); m permuted to [batch comps][rots][M][n] and passed through
 ksntt_mac against w_hat as [1][1][rots][M][n] with k = {1}, terms = rots; the c_0 term padded with
 zero P limbs, passed through ksntt_mac against the host-computed w_hat (P mod m_l), summed over r
-the same way and added to component 0 mod m_l on the host in uint64.  Up to n = 512 also with the
-Python-integer reference tests/lintrans_ref.py.  Operands are device-resident, every output is
+the same way and added to component 0 mod m_l on the host in uint64.  And, on every output word at
+every degree, with the CPU reference (tests/full_ref.py over tests/lintrans_ref.py), which shares
+no code with the device: the composition beside it says which side is wrong.  Operands are device-resident, every output is
 preset to the sentinel (tests/guarded.py).  The shapes are the smallest at which the kernel can go
 wrong (tests/lintrans_cases.py).  Any canonical vector is a transform of something, so the inputs
 are seeded canonical words."""
@@ -16,6 +17,7 @@ import numpy as np
 import pytest
 
 import bconv_ref as B
+import full_ref as F
 import guarded as G
 import hoist_ref as H
 import lintrans_cases as C
@@ -101,8 +103,7 @@ def test_apply_parity(case, torch_cuda):
             C.kernel_name(case.bits, case.comps, case.weighted)
         got = _apply(torch_cuda, lt, a, b, case.ks, w, c0)
         assert np.array_equal(got, ref.composition(kn, a, b, case.ks, q, p, w, c0))
-    if case.n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.apply(a, b, case.ks, q, p, w, c0))
+    F.assert_equal(got, F.reference("lintrans", "apply", a, b, case.ks, q, p, w, c0), _id(case))
 
 
 @pytest.mark.parametrize("case", C.worst_cases(), ids=_id)
@@ -121,6 +122,7 @@ def test_worst_case_ranges(fill, case, torch_cuda):
     c0 = np.broadcast_to(top[:L], (case.batch, L, n)).copy()
     with nttmul.NttLinTrans(n, q, p) as lt:
         got = _apply(torch_cuda, lt, a, b, case.ks, w, c0)
+    F.assert_equal(got, F.reference("lintrans", "apply", a, b, case.ks, q, p, w, c0), _id(case))
     if fill == "zero":
         assert not got.any()
         return
@@ -142,44 +144,37 @@ def test_identities(bits, torch_cuda):
         for r, k in enumerate(case.ks):
             got = _apply(torch_cuda, lt, a, b[r:r + 1], (k,))
             assert np.array_equal(got, kn.mac(a, b[r:r + 1], (k,))[:, 0])
+            F.assert_equal(got, F.reference("ksntt", "mac", a, b[r:r + 1], (k,), q + p)[:, 0], r)
         for z in (None, c0):
-            assert np.array_equal(_apply(torch_cuda, lt, a, b, case.ks, None, z),
-                                  _apply(torch_cuda, lt, a, b, case.ks, ones, z))
+            got = _apply(torch_cuda, lt, a, b, case.ks, None, z)
+            assert np.array_equal(got, _apply(torch_cuda, lt, a, b, case.ks, ones, z))
+            F.assert_equal(got, F.reference("lintrans", "apply", a, b, case.ks, q, p, None, z))
 
 
 @pytest.mark.parametrize("bits", (32, 64))
 @pytest.mark.parametrize("n", C.CHAIN_N)
 def test_the_linear_transform_end_to_end(n, bits, torch_cuda):
     """NttKeySwitch.modup -> NttLinTrans.apply -> NttModDown.moddown over batch 2 polynomials on
-    lintrans_ref.chain's keys, c_0 and weights: at n = 256 bit for bit the forward of the
-    Python-integer chain's output; at both n within hoist_ref.chain_bound() (the derivation is
+    lintrans_ref.chain's keys, c_0 and weights: at both n every stage bit for bit the CPU chain's,
+    in the NTT domain, and within hoist_ref.chain_bound() (the derivation is
     tests/test_lintrans_ref.py's)."""
     torch = torch_cuda
-    small = n <= C.REF_MAX_N
-    ch = ref.chain(n, bits) if small else dict(H.chain(n, bits))
+    ch = ref.chain(n, bits)
     q, p, alpha, ks = ch["q"], ch["p"], ch["alpha"], ch["ks"]
     batch, L, M = ch["x"].shape[0], len(q), len(q) + len(p)
     Ctx = nttmul.RnsHoistContext if n <= 4096 else nttmul.RnsMpHoistContext
-    with Ctx(n, q) as low, Ctx(n, q + p) as big, nttmul.NttKeySwitch(n, q, p, alpha) as kn, \
+    with Ctx(n, q) as low, nttmul.NttKeySwitch(n, q, p, alpha) as kn, \
             nttmul.NttLinTrans(n, q, p) as lt, nttmul.NttModDown(n, q, p) as md:
-        if not small:                       # the same construction, transforms on the device
-            rng = np.random.default_rng(7 * n + bits)
-            ch["c0"] = B.random_words(rng, q, batch, n, _dt(bits))
-            ch["ws"] = ref.signed_weights(rng, n, len(ks))
-            wc = np.array([[[v % m for v in poly] for m in q + p] for poly in ch["ws"]],
-                          dtype=_dt(bits))
-            ch["w_hat"], ch["c0_hat"] = big.forward(wc), low.forward(ch["c0"])
-        else:
-            assert np.array_equal(low.forward(ch["c0"]), ch["c0_hat"])
+        assert np.array_equal(low.forward(ch["c0"]), ch["c0_hat"])
         up_hat = kn.modup(low.forward(ch["x"]))
         assert np.array_equal(up_hat, ch["up_hat"])
         mid = _apply(torch, lt, up_hat, ch["key_hat"], ks, ch["w_hat"], ch["c0_hat"])
         out_hat = md.moddown(mid.reshape(batch * 2, M, n))
         back = low.inverse(out_hat).reshape(batch, 2, L, n)
-        if small:
-            assert np.array_equal(mid, ch["mid_lt"])
-            assert np.array_equal(out_hat, low.forward(ch["out_lt"].reshape(batch * 2, L, n)))
-            assert np.array_equal(back, ch["out_lt"])
+        F.assert_equal(mid, ch["mid_lt"], "apply")
+        F.assert_equal(out_hat, H.forward(ch["out_lt"].reshape(batch * 2, L, n), q), "moddown")
+        assert np.array_equal(out_hat, low.forward(ch["out_lt"].reshape(batch * 2, L, n)))
+        assert np.array_equal(back, ch["out_lt"])
     errs = ref.chain_errors(ch, back)
     print("lintrans chain errors", n, bits, errs, "bound", H.chain_bound())
     assert max(errs) <= H.chain_bound()
@@ -234,6 +229,8 @@ def test_host_form_equals_the_device_form(n, batch, bits, torch_cuda):
             host = lt.apply(a, b, case.ks, wv, zv)
             assert host.dtype == _dt(bits) and np.array_equal(host, dev)
             assert np.array_equal(dev, ref.composition(kn, a, b, case.ks, q, p, wv, zv))
+            F.assert_equal(dev, F.reference("lintrans", "apply", a, b, case.ks, q, p, wv, zv),
+                           (n, batch, bits, ww, zz))
         assert lt.apply(a[:0], b, case.ks, w, c0[:0]).shape == (0, 2, L + K, n)
         with pytest.raises(ValueError):
             lt.apply(a, b[:1], case.ks)

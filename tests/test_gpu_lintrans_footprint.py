@@ -4,7 +4,7 @@ the `_device` entry point and the host form run between sentinel guards at addre
 the word and to nothing larger; afterwards no guard word has changed, every input is bit-identical
 to the copy taken before the call, exactly the output's words are written (the arena's output is
 that long, every word after it is a guard, and no word of it keeps the sentinel), and the result
-is right bit for bit.
+is right bit for bit: the CPU reference of every output word (tests/full_ref.py) at both degrees.
 
 The rows are tests/lintrans_cases.py footprint_cases(): n = 256 and n = 8192 with batch V + 1 (a
 partial last workgroup), (L, K) = (3, 2), w_hat and c0_hat given and NULL in turn, both word
@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import bconv_ref as B
+import full_ref as F
 import guarded as G
 import lintrans_cases as C
 import lintrans_ref as ref
@@ -89,10 +90,10 @@ def test_apply(param, torch_cuda):
             assert f.entry == "nttmul_lintrans_apply" + ("" if f.host else "_device")
             wv, zv = (w if c.weighted else None), (c0 if c.c0 else None)
             if (c.weighted, c.c0) not in want:   # the reference once per form of the call
-                if n <= C.REF_MAX_N:
-                    want[c.weighted, c.c0] = ref.apply(a, b, ks, q, p, wv, zv)
-                else:
-                    want[c.weighted, c.c0] = ref.composition(kn, a, b, ks, q, p, wv, zv)
+                want[c.weighted, c.c0] = F.reference("lintrans", "apply", a, b, ks, q, p, wv, zv)
+                if n > 512:                      # the composition beside it: which side is wrong
+                    F.assert_equal(ref.composition(kn, a, b, ks, q, p, wv, zv),
+                                   want[c.weighted, c.c0], ("the composition", f))
             operands = dict(out=int(np.prod(shape)), a=a, b=b)
             if c.weighted:
                 operands["w"] = w

@@ -5,7 +5,11 @@ classes) holds at least 2 * 8192 waves, with the smallest batch that meets it an
 last workgroup.  Inputs are made on the device, the output is preset to a sentinel no canonical
 word equals, every word is compared on the device with the composition of ksntt_mac calls and the
 scale_cases sample with tests/lintrans_ref.py.  A further test passes an a_hat just over 4 GiB and
-compares with the same call in chunks below 1 GiB."""
+compares with the same call in chunks below 1 GiB.
+
+The batches here exist to fill the machine (at least 16384 waves per launch), so an integer
+reference of every output word would be minutes of CPU: this file keeps its sampled check.  The CPU
+reference of every output word, at every degree, is held in test_gpu_lintrans.py (tests/full_ref.py)."""
 import numpy as np
 import pytest
 

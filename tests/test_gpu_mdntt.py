@@ -1,9 +1,11 @@
 """GPU parity of ModDown on NTT-domain limbs (include/nttmul_mdntt.h, lib/libnttmul_mdntt.so,
 csrc/mdntt_dev.hpp k_mdntt_*): two launches per sub-batch up to n = 4096, four above.
 
-Every case is compared bit for bit with the device composition it replaces -- inverse over Q u P
-(nttmul.RnsHoistContext / RnsMpHoistContext), KeySwitchBasis.moddown, forward over Q -- and up to
-n = 512 with the Python-integer reference tests/mdntt_ref.py as well.  Every output is preset to
+Every case is compared bit for bit, on every output word and at every degree, with the CPU
+reference (tests/full_ref.py over tests/mdntt_ref.py and the oracle's transforms), which shares no
+code with the device; and beside it with the device composition it replaces -- inverse over Q u P
+(nttmul.RnsHoistContext / RnsMpHoistContext), KeySwitchBasis.moddown, forward over Q -- which says
+which side is wrong when the two disagree.  Every output is preset to
 the sentinel in a guarded arena (tests/guarded.py).  The shapes are the smallest at which the
 kernels can go wrong (tests/mdntt_cases.py).  Any canonical vector is a transform of something, so
 the inputs are seeded canonical words."""
@@ -13,6 +15,7 @@ import numpy as np
 import pytest
 
 import bconv_ref as B
+import full_ref as F
 import guarded as G
 import mdntt_cases as C
 import mdntt_ref as ref
@@ -82,6 +85,11 @@ def _input(case, seed):
     return B.random_words(np.random.default_rng(seed), q + p, case.batch, case.n, _dt(case.bits))
 
 
+def _want(x_hat, q, p):
+    """The CPU reference of every output word."""
+    return F.reference("mdntt", "moddown", x_hat, q, p)
+
+
 def _id(case):
     return f"u{case.bits}-n{case.n}x{case.batch}-{case.L}.{case.K}" + \
         ("-small" if case.moduli else "")
@@ -105,8 +113,7 @@ def test_parity(case, torch_cuda):
             (case.n, case.n, 1, C.DEFAULT_SCRATCH_MB)
         got = _call(torch_cuda, md, x)
     assert np.array_equal(got, _compose(torch_cuda, case.n, q, p, x))
-    if case.n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.moddown(x, q, p))
+    F.assert_equal(got, _want(x, q, p), _id(case))
 
 
 @pytest.mark.parametrize("bits", (32, 64))
@@ -135,15 +142,15 @@ def test_worst_case_ranges(fill, n, bits, torch_cuda):
         for l, m in enumerate(q):
             want = (x[:, l, :].astype(object) * pow(P, -1, m) % m).astype(_dt(bits))
             assert np.array_equal(got[:, l, :], want), l
-    if n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.moddown(x, q, p))
+    F.assert_equal(got, _want(x, q, p), (fill, n, bits))
 
 
 @pytest.mark.parametrize("bits", (32, 64))
 @pytest.mark.parametrize("n,L", C.RESCALE)
 def test_rescale_is_the_exact_floor(n, L, bits, torch_cuda):
     """K = 1: the inverse transform of out is floor(X / p) mod q_l for random big integers X in
-    [0, Q p), the ends of the range among them."""
+    [0, Q p), the ends of the range among them; and out itself is the CPU reference's, word for
+    word."""
     torch = torch_cuda
     batch = C.RESCALE_BATCH
     case = C.Case(bits, n, batch, L, 1)
@@ -158,6 +165,8 @@ def test_rescale_is_the_exact_floor(n, L, bits, torch_cuda):
         x_hat = big.forward(x)
         got = _call(torch, md, x_hat)
         back = low.inverse(got)
+    assert np.array_equal(x_hat, ref.forward(x, ext))
+    F.assert_equal(got, _want(x_hat, q, p), (n, L, bits))
     for b in range(batch):
         assert np.array_equal(back[b].astype(object), ref.rescale_floor(X[b], q, p[0])), b
 
@@ -173,13 +182,16 @@ def test_sub_batches_and_two_streams(torch_cuda):
         with nttmul.NttModDown(case.n, q, p, scratch_mb=1) as md:
             assert md.info.scratch_mb == 1
             small = _input(case._replace(batch=1), 3)
-            assert np.array_equal(_call(torch, md, small),
-                                  _compose(torch, case.n, q, p, small))
+            got = _call(torch, md, small)
+            assert np.array_equal(got, _compose(torch, case.n, q, p, small))
+            F.assert_equal(got, _want(small, q, p), (case, "one polynomial"))
             x = _input(case, 4)                 # the scratch grows to a whole sub-batch
             want_x = _compose(torch, case.n, q, p, x)
             assert np.array_equal(_call(torch, md, x), want_x)
+            F.assert_equal(want_x, _want(x, q, p), (case, "sub-batches"))
             y = _input(case, 5)
             want_y = _compose(torch, case.n, q, p, y)
+            F.assert_equal(want_y, _want(y, q, p), (case, "second stream"))
             tdt = torch.int64
             dx, dy = _to_dev(torch, x, 64), _to_dev(torch, y, 64)
             ox = torch.empty(want_x.size, dtype=tdt, device="cuda")
@@ -207,6 +219,7 @@ def test_validate_flag_checks_each_word_against_its_own_limb(bits, torch_cuda):
     with nttmul.NttModDown(n, q, p, validate=True) as strict, nttmul.NttModDown(n, q, p) as lax:
         want = _compose(torch, n, q, p, good)
         assert np.array_equal(_call(torch, strict, good), want)
+        F.assert_equal(want, _want(good, q, p), bits)
         for limb in (1, L + K - 1):
             bad = good.copy()
             bad[batch - 1, limb, n - 1] = ext[limb]
@@ -236,6 +249,7 @@ def test_host_form_equals_the_device_form(n, batch, bits, torch_cuda):
         with pytest.raises(ValueError):
             md.moddown(np.zeros((1, L, n), dtype=_dt(bits)))
     assert np.array_equal(dev, _compose(torch_cuda, n, q, p, x))
+    F.assert_equal(dev, _want(x, q, p), (n, batch, bits))
 
 
 def test_device_path_rules(torch_cuda):
@@ -248,7 +262,7 @@ def test_device_path_rules(torch_cuda):
         side = torch.cuda.Stream()
         x = _input(case, 5)
         got = _call(torch, md, x, stream=side.cuda_stream)
-        assert np.array_equal(got, ref.moddown(x, q, p))
+        F.assert_equal(got, _want(x, q, p))
         out = torch.full((C.N,), 7, dtype=torch.int32, device="cuda")
         md.moddown_device(out, out, 0)                               # batch = 0: a no-op
         torch.cuda.synchronize()

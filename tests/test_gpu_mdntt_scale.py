@@ -5,7 +5,11 @@ waves and ends in a partial last workgroup where the kernel takes several units 
 Inputs are made on the device, the output is preset to a sentinel no canonical word equals, every
 word is compared with the device composition (inverse over Q u P, KeySwitchBasis.moddown, forward
 over Q) and the scale_cases sample with tests/mdntt_ref.py.  Two further tests pass an x_hat just
-over 4 GiB and compare with the same call in chunks below 1 GiB."""
+over 4 GiB and compare with the same call in chunks below 1 GiB.
+
+The batches here exist to fill the machine (at least 16384 waves per launch), so an integer
+reference of every output word would be minutes of CPU: this file keeps its sampled check.  The CPU
+reference of every output word, at every degree, is held in test_gpu_mdntt.py (tests/full_ref.py)."""
 import numpy as np
 import pytest
 

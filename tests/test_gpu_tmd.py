@@ -1,15 +1,17 @@
 """GPU parity of BGV's plaintext-preserving ModDown (include/nttmul_tmd.h, lib/libnttmul_tmd.so,
 csrc/tmd_dev.hpp k_tmd_*): two launches per sub-batch up to n = 4096, four above.
 
-Up to n = 512 every coefficient is compared bit for bit with tests/tmd_ref.py in Python integers;
-at every kernel size the output is held to the identity out = nttmul_mdntt_moddown(x_hat) -
-forward(u mod q_l) (tests/tmd_gpu.py).  Every output is preset to the sentinel in a guarded arena
+At every degree every word of the NTT-domain output is compared bit for bit with the CPU reference
+(tests/full_ref.py over tests/tmd_ref.py and the oracle's transforms), which shares no code with
+the device; beside it the output is held to the identity out = nttmul_mdntt_moddown(x_hat) -
+forward(u mod q_l) (tests/tmd_gpu.py), which says which side is wrong.  Every output is preset to the sentinel in a guarded arena
 (tests/guarded.py).  Everything is integer arithmetic: no comparison is conditional on the data."""
 from math import prod
 
 import numpy as np
 import pytest
 
+import full_ref as F
 import hoist_cases
 import hoist_ref as H
 import ks_ref
@@ -46,13 +48,13 @@ def test_parity(case, torch_cuda):
             (case.n, case.n, 1, C.DEFAULT_SCRATCH_MB)
         assert (tm.info.t, tm.msg_factor) == (case.t, pow(prod(p), -1, case.t))
         got = _call(torch_cuda, tm, x)
-    assert np.array_equal(got, ref.moddown(x, q, p, case.t))
+    F.assert_equal(got, F.reference("tmd", "moddown", x, q, p, case.t), _id(case))
 
 
 @pytest.mark.parametrize("case", C.identity_cases() + C.degree_cases(), ids=_id)
 def test_the_identity_at_every_kernel_size(case, torch_cuda):
-    """out == mdntt_moddown(x_hat) - forward(u mod q_l), u from the library's own inverse of the P
-    limbs and Python integers."""
+    """Every word is the CPU reference's; and out == mdntt_moddown(x_hat) - forward(u mod q_l), u
+    from the library's own inverse of the P limbs and Python integers."""
     q, p = C.moduli_of(case)
     x = C.seeded_input(case)
     with nttmul.NttPlainModDown(case.n, q, p, case.t) as tm:
@@ -166,7 +168,9 @@ def test_validate_flag_leaves_the_output_untouched(bits, torch_cuda):
     good = C.seeded_input(case)
     with nttmul.NttPlainModDown(n, q, p, t, validate=True) as strict, \
             nttmul.NttPlainModDown(n, q, p, t) as lax:
-        assert np.array_equal(_call(torch, strict, good), _call(torch, lax, good))
+        got = _call(torch, strict, good)
+        assert np.array_equal(got, _call(torch, lax, good))
+        _check(n, q, p, t, good, got)
         for limb in (1, len(mods) - 1):
             bad = good.copy()
             bad[batch - 1, limb, n - 1] = mods[limb]
@@ -248,11 +252,12 @@ def test_the_key_switch_keeps_the_error_a_multiple_of_t(n, bits, t, torch_cuda):
         up_hat = kn.modup(low.forward(ch["x"]))
         mid_hat = kn.mac(up_hat, ch["key_hat"], ks)
         flat = np.ascontiguousarray(mid_hat.reshape(batch * rots * 2, L + K, n))
-        back = low.inverse(_call(torch_cuda, tm, flat)).reshape(batch, rots, 2, L, n)
+        out_hat = _call(torch_cuda, tm, flat)
+        back = low.inverse(out_hat).reshape(batch, rots, 2, L, n)
         floor = low.inverse(md.moddown(flat)).reshape(batch, rots, 2, L, n)
-    if n <= C.REF_MAX_N:
-        assert np.array_equal(back, ref.moddown_coeff(ch["mid"].reshape(-1, L + K, n), q, p, t)
-                              .reshape(back.shape))
+    want = ref.moddown_coeff(ch["mid"].reshape(-1, L + K, n), q, p, t)
+    F.assert_equal(out_hat, H.forward(want, q), (n, bits, t))
+    assert np.array_equal(back, want.reshape(back.shape))
     es = C.chain_error_polys(ch, back)
     assert len(es) == batch * rots
     assert all(v % t == 0 for e in es for v in e)

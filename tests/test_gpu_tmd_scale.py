@@ -8,7 +8,11 @@ out = nttmul_mdntt_moddown(x_hat) - forward(u mod q_l), formed on the device: th
 inverse of the P limb, u in 64-bit integer arithmetic (K = 1: y = the coefficient itself, and
 (y mod t) g < 2^64), the library's forward transform and the floor form of lib/libnttmul_mdntt.so.
 A sample of polynomials (tests/scale_cases.py sample) is held to the Python integers of
-tests/tmd_ref.py on top."""
+tests/tmd_ref.py on top.
+
+The batches here exist to fill the machine (at least 16384 waves per launch), so an integer
+reference of every output word would be minutes of CPU: this file keeps its sampled check.  The CPU
+reference of every output word, at every degree, is held in test_gpu_tmd.py (tests/full_ref.py)."""
 import numpy as np
 import pytest
 

@@ -2,10 +2,11 @@
 lib/libnttmul_xconv.so, csrc/xconv_dev.hpp k_xconv_*): two launches per sub-batch up to n = 4096,
 four above.
 
-Every case is compared with the device composition -- the library's own inverse transforms over
-the input's limbs, the reference arithmetic of tests/xconv_ref.py in Python integers on a sample of
-coefficients (first, last, one per 1/64), the library's inverse over Q of the output -- and up to
-n = 512 bit for bit with tests/xconv_ref.py on every coefficient.  Every output is preset to the
+Every case is compared, on every word of the NTT-domain output and at every degree, with the CPU
+reference (tests/full_ref.py over tests/xconv_ref.py and the oracle's transforms), which shares no
+code with the device; and beside it with the device composition on every coefficient -- the
+library's own inverse transforms over the input's limbs, the same reference arithmetic, the
+library's inverse over Q of the output (tests/xconv_gpu.py check).  Every output is preset to the
 sentinel in a guarded arena (tests/guarded.py).  The seeded inputs hold no coefficient inside the
 guard band (tests/test_xconv_ref.py), so every comparison is exact; the band itself is the edge
 polynomial's test."""
@@ -15,12 +16,12 @@ from math import prod
 import numpy as np
 import pytest
 
+import full_ref as F
 import hoist_ref as H
-import mdntt_ref
 import nttmul
 import xconv_cases as C
 import xconv_ref as ref
-from xconv_gpu import (call as _call, check_composition as _check_composition, ctx as _ctx,
+from xconv_gpu import (call as _call, check as _check, ctx as _ctx,
                        dt as _dt, to_dev as _to_dev)
 
 pytestmark = pytest.mark.gpu
@@ -50,9 +51,7 @@ def test_parity(case, torch_cuda):
             (case.n, case.n, 1, C.DEFAULT_SCRATCH_MB)
         assert (xc.info.scale, xc.info.band_log2) == (case.t, C.BAND_LOG2)
         got = _call(torch_cuda, xc, case.op, x)
-    _check_composition(case.op, case.n, q, p, case.t, x, got)
-    if case.n <= C.REF_MAX_N:
-        assert np.array_equal(got, getattr(ref, case.op)(x, q, p, case.t))
+    _check(case.op, case.n, q, p, case.t, x, got)
 
 
 # ---- the edge polynomial: the test of the correction itself -------------------------------------
@@ -164,23 +163,25 @@ def test_consistency_with_the_floor_moddown(L, K, bits, torch_cuda):
 
 
 @pytest.mark.parametrize("bits", (32, 64))
-@pytest.mark.parametrize("n,L", ((256, 1), (256, 3), (8192, 3)))
+@pytest.mark.parametrize("n,L", C.RESCALE)
 def test_rescale_is_the_exact_rounding(n, L, bits, torch_cuda):
     """K = 1, t = 1: the inverse transform of out is round(X / p) mod q_l for random big integers X
-    in [0, Q p), the ends of the range among them."""
+    in [0, Q p), the ends of the range among them; and out itself is the CPU reference's, word for
+    word."""
     torch = torch_cuda
-    batch = 2
-    case = C.Case("moddown", bits, n, batch, L, 1)
+    batch = C.RESCALE_BATCH
+    case = C.rescale_case(bits, n, L)
     q, p = C.moduli_of(case)
     ext = q + p
-    bound = prod(int(v) for v in ext)
-    rng = np.random.default_rng(n * L + bits)
-    X = [mdntt_ref.big_integers(rng, n, bound) for _ in range(batch)]
-    x = np.stack([mdntt_ref.residues(Xb, ext, _dt(bits)) for Xb in X])
+    X, x = C.rescale_input(case)
     assert ref.count_in_band(x[:, L:], p, 1, Fraction(1, 1 << C.BAND_LOG2)) == 0
     Ctx = _ctx(n)
     with Ctx(n, ext) as big, Ctx(n, q) as low, nttmul.NttExactConv(n, q, p) as xc:
-        back = low.inverse(_call(torch, xc, "moddown", big.forward(x)))
+        x_hat = big.forward(x)
+        got = _call(torch, xc, "moddown", x_hat)
+        back = low.inverse(got)
+    assert np.array_equal(x_hat, H.forward(x, ext))
+    F.assert_equal(got, F.reference("xconv", "moddown", x_hat, q, p, 1), (n, L, bits))
     for b in range(batch):
         assert np.array_equal(back[b].astype(object), ref.moddown_values(X[b], q, p)), b
 
@@ -204,8 +205,9 @@ def test_the_rounded_key_switch_halves_the_noise(n, bits, torch_cuda):
         flat = np.ascontiguousarray(mid_hat.reshape(batch * rots * 2, L + len(p), n))
         out_hat = _call(torch_cuda, xc, "moddown", flat)
         back = low.inverse(out_hat).reshape(batch, rots, 2, L, n)
-    assert np.array_equal(back, ref.moddown_coeff(ch["mid"].reshape(-1, L + len(p), n), q, p)
-                          .reshape(back.shape))
+    want = ref.moddown_coeff(ch["mid"].reshape(-1, L + len(p), n), q, p)
+    F.assert_equal(out_hat, H.forward(want, q), (n, bits))
+    assert np.array_equal(back, want.reshape(back.shape))
     errs = H.chain_errors(ch, back)
     assert 2 * max(errs) < 1 + hoist_cases.CHAIN_H, errs
 
@@ -225,7 +227,7 @@ def test_sub_batches(case, torch_cuda):
         one = _call(torch_cuda, xc, case.op, x[:1])   # the scratch grows after this call
         got = _call(torch_cuda, xc, case.op, x)
     assert np.array_equal(one[0], got[0])
-    _check_composition(case.op, case.n, q, p, case.t, x, got)
+    _check(case.op, case.n, q, p, case.t, x, got)
 
 
 @pytest.mark.parametrize("op", C.OPS)
@@ -244,7 +246,7 @@ def test_host_form_equals_the_device_form(n, batch, bits, op, torch_cuda):
         assert getattr(xc, op)(x[:0]).shape == (0, L, n)
         with pytest.raises(ValueError):
             getattr(xc, op)(np.zeros((1, L + K + 1, n), dtype=_dt(bits)))
-    _check_composition(op, n, q, p, 1, x, dev)
+    _check(op, n, q, p, 1, x, dev)
 
 
 @pytest.mark.parametrize("op", C.OPS)
@@ -262,7 +264,9 @@ def test_validate_flag_leaves_the_output_untouched(bits, op, torch_cuda):
     good = C.seeded_input(case)
     with nttmul.NttExactConv(n, q, p, validate=True) as strict, \
             nttmul.NttExactConv(n, q, p) as lax:
-        assert np.array_equal(_call(torch, strict, op, good), _call(torch, lax, op, good))
+        got = _call(torch, strict, op, good)
+        assert np.array_equal(got, _call(torch, lax, op, good))
+        _check(op, n, q, p, 1, good, got)
         for limb in (1, len(mods) - 1):
             bad = good.copy()
             bad[batch - 1, limb, n - 1] = mods[limb]
@@ -285,7 +289,7 @@ def test_device_path_rules(torch_cuda):
         side = torch.cuda.Stream()
         x = C.seeded_input(case)
         got = _call(torch, xc, "moddown", x, stream=side.cuda_stream)
-        assert np.array_equal(got, ref.moddown(x, q, p, case.t))
+        F.assert_equal(got, F.reference("xconv", "moddown", x, q, p, case.t))
         out = torch.full((C.N,), 7, dtype=torch.int32, device="cuda")
         for op in C.OPS:
             fn = getattr(xc._lib, f"nttmul_xconv_{op}_device")

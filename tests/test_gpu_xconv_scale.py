@@ -6,8 +6,12 @@ in a partial last workgroup where the kernel takes several units per workgroup. 
 on the device and the output is preset to a sentinel no canonical word equals.  Every word is
 compared with the same context's call on pieces of the batch that start at other workgroups (a
 call's result is a function of its input alone, inside the guard band as well), and the
-scale_cases sample of polynomials with the device composition of tests/xconv_gpu.py, the sampled
-polynomials holding no coefficient inside the band."""
+scale_cases sample of polynomials with the device composition below on xconv_cases.sample_indices,
+the sampled polynomials holding no coefficient inside the band.
+
+The batches here exist to fill the machine, so an integer reference of every word would be minutes
+of CPU: this file keeps the sampled check.  The CPU reference of every output word, at every
+degree, is test_gpu_xconv.py's (tests/full_ref.py)."""
 import numpy as np
 import pytest
 
@@ -15,7 +19,7 @@ import nttmul
 import scale_cases as S
 import xconv_cases as C
 import xconv_ref as ref
-from xconv_gpu import check_composition, ctx
+from xconv_gpu import ctx
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +46,19 @@ def _random_device(torch, moduli, batch, n, bits, seed):
 
 def _host(t, bits):
     return t.cpu().numpy().view(np.uint32 if bits == 32 else np.uint64)
+
+
+def check_composition(op, n, q, p, t, src, got):
+    """got against the reference on the sampled coefficients, through the library's transforms:
+    its inverse over the input's limbs, tests/xconv_ref.py's arithmetic on
+    xconv_cases.sample_indices (first, last, one per 1/64), its inverse over Q of the output."""
+    idx = C.sample_indices(n)
+    Ctx = ctx(n)
+    with Ctx(n, tuple(p) if op == "extend" else tuple(q) + tuple(p)) as wide, Ctx(n, q) as low:
+        coef = wide.inverse(src)
+        back = low.inverse(got)
+    fn = ref.extend_coeff if op == "extend" else ref.moddown_coeff
+    assert np.array_equal(back[:, :, idx], fn(coef[:, :, idx], q, p, t))
 
 
 def launches(case):

@@ -169,3 +169,20 @@ def test_every_entry_point_that_writes_caller_memory_has_a_footprint_row():
         assert got == {(b, n, batch) for b in (32, 64) for n, batch in C.FP_SIZES}
     assert all((f.host == "host") == (not f.entry.endswith("_device")) for f in rows)
     assert all(f.case.L < C.L_TOP for f in rows)
+
+
+def test_every_additional_kernel_is_launched_by_a_case_held_to_the_cpu_reference(xconv, level):
+    """The mirror reports the cases whose every output word a GPU test compares with the CPU
+    reference (referenced_cases(): at every n, tests/full_ref.py); the cases full_ref.SUBSET holds
+    on a part of their batch only do not count, and are at most one in ten.  Every kernel this
+    library adds over its predecessor is launched by one of the rest."""
+    import full_ref
+    cases = C.referenced_cases()
+    assert cases and all(c in C.all_cases() for c in cases[:8] + cases[-8:])
+    whole = [c for c in cases if not full_ref.on_subset("level", c)]
+    assert 10 * (len(cases) - len(whole)) <= len(cases)
+    held = {k for c in whole for k in C.kernels_of(c)}
+    excused = {k for k in level if any(re.fullmatch(pat, k) for pat, _ in
+                                        getattr(C, "UNREACHABLE", ()))}
+    extra = set(level) - set(xconv)
+    assert extra and sorted(extra - held - excused) == []

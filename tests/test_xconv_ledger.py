@@ -128,10 +128,8 @@ def test_the_cases_cover_what_the_issue_names():
                            if (c.L, c.K) == C.DEGREE_SHAPE and c.n > 256)
     assert C.SCALES == (1, 65537) and C.EDGE_N == (256, 8192) and C.EDGE_K == (1, 2, 5)
     assert C.CHAIN_N == (256, 8192)
-    assert len(C.sample_indices(256)) >= 64 and {0, 255} <= set(C.sample_indices(256))
-    for n in C.ALL_N:
-        idx = C.sample_indices(n)
-        assert {i * 64 // n for i in idx} == set(range(64)) and {0, n - 1} <= set(idx)
+    # the sample the scale file keeps: tests/test_full_ref.py holds its definition
+    assert set(C.parity_cases()) <= set(C.referenced_cases())
 
 
 def test_the_scale_cases_meet_the_rule_of_scale_cases():
@@ -168,3 +166,20 @@ def test_every_entry_point_that_writes_caller_memory_has_a_footprint_row():
         assert got == {(b, n, batch, L, K) for b in (32, 64) for n, batch in C.FP_SIZES
                        for L, K in C.FP_SHAPES}
     assert all((f.host == "host") == (not f.entry.endswith("_device")) for f in rows)
+
+
+def test_every_additional_kernel_is_launched_by_a_case_held_to_the_cpu_reference(ctmul, xconv):
+    """The mirror reports the cases whose every output word a GPU test compares with the CPU
+    reference (referenced_cases(): at every n, tests/full_ref.py); the cases full_ref.SUBSET holds
+    on a part of their batch only do not count, and are at most one in ten.  Every kernel this
+    library adds over its predecessor is launched by one of the rest."""
+    import full_ref
+    cases = C.referenced_cases()
+    assert cases and all(c in C.all_cases() for c in cases[:8] + cases[-8:])
+    whole = [c for c in cases if not full_ref.on_subset("xconv", c)]
+    assert 10 * (len(cases) - len(whole)) <= len(cases)
+    held = {k for c in whole for k in C.kernels_of(c)}
+    excused = {k for k in xconv if any(re.fullmatch(pat, k) for pat, _ in
+                                        getattr(C, "UNREACHABLE", ()))}
+    extra = set(xconv) - set(ctmul)
+    assert extra and sorted(extra - held - excused) == []

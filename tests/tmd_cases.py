@@ -30,7 +30,6 @@ Case = namedtuple("Case", "bits n batch L K t validate scratch_mb moduli",
                   defaults=(False, 0, None))
 
 REF_N = (256, 512)                            # every coefficient in Python integers
-REF_MAX_N = 512
 REF_BATCH = 3                                 # a workgroup ends partial
 SHAPES = ((1, 1), (3, 1), (4, 2), (3, 3), (2, 5))
 IDENTITY_N = (256, 1024, 4096, 8192, 65536)   # every kernel size: L1 = 1 and 4 above 4096
@@ -139,15 +138,21 @@ def bases_cases():
             for prof in BASES_PROFILES for n in BASES_N for L, K in BASES_SHAPES for t in BASES_T]
 
 
-def all_cases():
+def referenced_cases():
+    """The cases whose every output word a GPU test holds to the CPU reference (tests/full_ref.py):
+    all but the scale and the 4 GiB cases, whose batches exist to fill the machine."""
     out = parity_cases() + identity_cases() + degree_cases() + subbatch_cases()
     out += [Case(bits, n, 1, EDGE_L, K, t) for bits in (32, 64) for n in EDGE_N for K in EDGE_K
             for t in plain_moduli(bits)]
     n, batch, shape = VALIDATE
     out += [Case(bits, n, batch, *shape, 65537, True) for bits in (32, 64)]
     out += [f.case for f in footprint_cases()]
-    out += scale_cases() + bases_cases()
+    out += bases_cases()
     return out
+
+
+def all_cases():
+    return referenced_cases() + scale_cases()
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """What the GPU tests of include/nttmul_tmd.h share (tests/test_gpu_tmd*.py): one call out of a
-guarded arena (tests/xconv_gpu.py call), and the identity the library is compared with where
-Python integers do not reach every coefficient through the oracle's transforms:
+guarded arena (tests/xconv_gpu.py call), the CPU reference of every output word at every degree
+(tests/full_ref.py), and the identity the library is compared with beside it:
 
     out = nttmul_mdntt_moddown(x_hat) - forward_Q(u mod q_l)       bit for bit
 
@@ -8,8 +8,8 @@ with u from the library's own inverse transforms of the P limbs and tests/tmd_re
 integers, the floor form from lib/libnttmul_mdntt.so and the forward transform the library's."""
 import numpy as np
 
+import full_ref as F
 import nttmul
-import tmd_cases as C
 import tmd_ref as ref
 from xconv_gpu import ctx, dt, to_dev  # noqa: F401
 
@@ -38,8 +38,8 @@ def identity_want(n, q, p, t, x):
 
 
 def check(n, q, p, t, x, got):
-    """The identity at every n, and every coefficient bit for bit in Python integers up to
-    REF_MAX_N."""
+    """Every word of the NTT-domain output against the CPU reference (tests/full_ref.py over
+    tests/tmd_ref.py and the oracle's transforms), bit for bit, at every n; and the identity
+    beside it, which says which side is wrong when the two disagree."""
+    F.assert_equal(got, F.reference("tmd", "moddown", x, q, p, t), (n, t))
     assert np.array_equal(got, identity_want(n, q, p, t, x))
-    if n <= C.REF_MAX_N:
-        assert np.array_equal(got, ref.moddown(x, q, p, t))

@@ -34,12 +34,13 @@ WIDE = MC.WIDE                                # batch 1; (1, 63): K + 1 = 64 pro
 CADENCE_K = {bits: tuple(k - 1 for k in ks if k > 1) for bits, ks in MC.CADENCE_K.items()}
 CADENCE_L = MC.CADENCE_L
 DEGREE_SHAPE = MC.DEGREE_SHAPE                # every n, batch 2 (1 at 65536)
-REF_MAX_N = MC.REF_MAX_N
 SAMPLE_STEP = 64                              # the composition samples first, last, one per 1/64
 SUBBATCH = MC.SUBBATCH
 VALIDATE = MC.VALIDATE
 HOST = MC.HOST
 HOST_SHAPE = MC.HOST_SHAPE
+RESCALE = ((256, 1), (256, 3), (8192, 3))     # (n, L): K = 1, t = 1, batch RESCALE_BATCH
+RESCALE_BATCH = 2
 EDGE_N = (256, 8192)
 EDGE_K = (1, 2, 5)
 EDGE_L = 2
@@ -150,7 +151,9 @@ def scale_cases():
             for bits in (32, 64) for op, n in rows]
 
 
-def all_cases():
+def referenced_cases():
+    """The cases whose every output word a GPU test holds to the CPU reference (tests/full_ref.py):
+    all but the scale and the 4 GiB cases, whose batches exist to fill the machine."""
     out = parity_cases() + subbatch_cases()
     n, batch, shape = VALIDATE
     out += [Case(op, bits, n, batch, *shape, 1, True) for op in OPS for bits in (32, 64)]
@@ -159,8 +162,11 @@ def all_cases():
     out += [Case("moddown", bits, n, 1, EDGE_L, K, t) for bits in (32, 64) for n in EDGE_N
             for K in EDGE_K for t in SCALES]
     out += [f.case for f in footprint_cases()]
-    out += scale_cases()
     return out
+
+
+def all_cases():
+    return referenced_cases() + scale_cases()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -194,6 +200,24 @@ def seeded_input(case, seed=None):
     return x
 
 
+def rescale_case(bits, n, L):
+    return Case("moddown", bits, n, RESCALE_BATCH, L, 1)
+
+
+def rescale_input(case):
+    """(X, x): per batch entry n seeded big integers in [0, Q p), the ends of the range among
+    them, and their residues [batch, L + 1, n] in coefficient order (the test transforms them)."""
+    import numpy as np
+    import mdntt_ref
+    from math import prod
+    q, p = moduli_of(case)
+    ext = q + p
+    rng = np.random.default_rng(case.n * case.L + case.bits)
+    dt = np.uint32 if case.bits == 32 else np.uint64
+    X = [mdntt_ref.big_integers(rng, case.n, prod(int(v) for v in ext)) for _ in range(case.batch)]
+    return X, np.stack([mdntt_ref.residues(Xb, ext, dt) for Xb in X])
+
+
 def sample_indices(n):
     """The coefficients the device composition is compared on: the first, the last, and one in
     each of the 64 blocks of n / 64 (at a position that moves with the block)."""
@@ -214,6 +238,11 @@ def seeded_gpu_inputs():
         yield case, seeded_input(case)
     for case in bases_cases():
         yield case, bases_input(case)
+    import hoist_ref as H
+    for bits in (32, 64):
+        for n, L in RESCALE:                  # coefficient order: the NTT-order input is its forward
+            case = rescale_case(bits, n, L)
+            yield case, H.forward(rescale_input(case)[1], sum(moduli_of(case), ()))
 
 
 # Mixed-size bases (tests/test_gpu_xconv_bases.py, tests/basis_cases.py): a case's `moduli` names a

@@ -1,14 +1,15 @@
 """What the GPU tests of include/nttmul_xconv.h share (tests/test_gpu_xconv*.py): one call out of
-a guarded arena, and the device composition the library is compared with where Python integers do
-not reach every coefficient -- the library's own inverse transforms over the input's limbs, the
-reference arithmetic of tests/xconv_ref.py on a sample of coefficients (first, last, one per 1/64),
-the library's inverse over Q of the output."""
+a guarded arena, and the two comparisons every result gets at every degree -- the NTT-domain output
+against the CPU reference of every word (tests/full_ref.py over tests/xconv_ref.py and the oracle's
+transforms, which share no code with the device), and beside it the device composition on every
+coefficient: the library's own inverse transforms over the input's limbs, the same reference
+arithmetic, the library's inverse over Q of the output.  The composition says which side is wrong
+when the first comparison fails."""
 import numpy as np
 
+import full_ref as F
 import guarded as G
 import nttmul
-import xconv_cases as C
-import xconv_ref as ref
 
 
 def dt(bits):
@@ -38,24 +39,16 @@ def call(torch, xc, op, src, stream=0):
     return arena.get("out", shape)
 
 
-def want_sampled(op, coef, q, p, t, idx):
-    """The reference on the coefficients idx of coef [batch, limbs, n] (coefficient order)."""
-    fn = ref.extend_coeff if op == "extend" else ref.moddown_coeff
-    return fn(coef[:, :, idx], q, p, t)
-
-
-def check_composition(op, n, q, p, t, src, got):
-    """got against the reference on the sampled coefficients, through the library's transforms."""
-    idx = C.sample_indices(n)
+def check(op, n, q, p, t, src, got):
+    """got [batch, L, n] against the CPU reference on every word of the NTT-domain output, bit for
+    bit, at every n; then the composition through the library's transforms, on every coefficient:
+    the library's inverse of the input is the oracle's, and its inverse of the output is the
+    reference's coefficients."""
+    src_coef, want_coef, want = F.conversion("xconv", op, src, q, p, t, with_input=True)
+    F.assert_equal(got, want, (op, n, t))
     Ctx = ctx(n)
     with Ctx(n, tuple(p) if op == "extend" else tuple(q) + tuple(p)) as wide, Ctx(n, q) as low:
         coef = wide.inverse(src)
         back = low.inverse(got)
-    assert np.array_equal(back[:, :, idx], want_sampled(op, coef, q, p, t, idx))
-
-
-def check(op, n, q, p, t, src, got):
-    """The composition at every n, and every coefficient bit for bit up to REF_MAX_N."""
-    check_composition(op, n, q, p, t, src, got)
-    if n <= C.REF_MAX_N:
-        assert np.array_equal(got, getattr(ref, op)(src, q, p, t))
+    assert np.array_equal(coef, src_coef), "the library's inverse of the input"
+    assert np.array_equal(back, want_coef), "the library's inverse of the output"
